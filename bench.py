@@ -1,9 +1,17 @@
 #!/usr/bin/env python3
 """bench.py -- Avro -> Arrow direct decode on MI355X: records/s + achieved HBM GB/s.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run does only what its headline needs: set-up (generate the records, copy them to HBM, load the schema's kernels),
+warm-up, the K timed steps and the line -- `metric`, `value`, `unit`, `ms_per_step`, `config` and `roofline`, all from those
+steps.  `--full` adds every other measurement and check listed below (the `overlapped` region, `config.sync_call_ms`,
+`two_pass` / `single_pass`, `config5_projection`, `cpu_baseline` + `parity_check`, `end_to_end`, `cold_start`,
+`other_configs`).  `--dump-outputs DIR` keeps the result of the last timed step and writes what its caller receives -- a
+fixed, seeded sample of rows of the Arrow batches, every column flattened to float32 / float64 arrays (dump_outputs) -- as
+DIR/<name>.npy, so that two builds can be compared output for output on the same inputs.
 
 A step = one pass of the hot path (k_size -> k_scan+layout -> k_emit -> k_publish, C ABI rh_decode_device) over one batch
 of synthetic Avro records that is ALREADY resident in HBM; the Arrow buffers are produced in HBM.  Workload
@@ -22,7 +30,7 @@ N > 1 (BASELINE.json config 5): the SAME seeded 10M-record list, its 8 reference
 collective: records are independent; RCCL carries the barrier, the MAX over rank times and the stats all-gather.
 `--scaling weak` keeps round 1's mode (every rank decodes its own 10M records of the stream).
 
-Rank 0 prints ONE JSON line (contract in the task statement) with these extra objects:
+Rank 0 prints ONE JSON line; with --full it carries these extra objects:
   roofline      k_emit (the dominant kernel): algorithmic bytes per launch / its mean launch duration,
                 measured with HIP events on the launch stream inside the timed steps, vs 8 TB/s HBM.  Also the whole
                 path against the same bytes (`path_frac`), the north star's own figure -- HBM READ bandwidth of the two
@@ -40,7 +48,7 @@ Rank 0 prints ONE JSON line (contract in the task statement) with these extra ob
                 (serial pack + one thread per chunk), timed on this box's host cores on the SAME records, best of 5:
                 with the workload's 8 chunks = 8 threads, and (`wide`) with min(64, cores) chunks.  Reported, not targeted.
   other_configs (N=1 only) compact lines of BASELINE configs 2 and 3, the full schema at 1M records and the Arrow -> Avro
-                direction (2M rows, device-resident), so that the driver's run of this default command carries them; and
+                direction (2M rows, device-resident), so that one --full run carries them; and
                 (round 6, `workload_line`) the walks OFF the friendly value distribution, each with kernel times, the tile
                 statistics of rh_engine_counters and a parity_check against the oracle: `full_realistic_10m` (microsecond
                 timestamps, epoch-second ints, snowflake ids, 1 % notes of 8 KiB and more, arrays of > 8,191 items),
@@ -105,6 +113,13 @@ def parse_args(argv=None):
     ap.add_argument("--rows", type=int, default=2_000_000, help="--direction encode: rows of the full schema")
     ap.add_argument("--scaling", default="strong", choices=["strong", "weak"],
                     help="N>1: strong = one list, whole chunks dealt to the ranks (BASELINE config 5); weak = the list per rank")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beside the headline: the overlapped region, sync_call_ms, the other launch "
+                         "form, config5_projection, cpu_baseline + parity_check, end_to_end, cold_start, other_configs (each still "
+                         "subject to its --no-* / --overlap-streams option)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the batches of the last timed step (rank 0's; a fixed, seeded sample of "
+                         "rows) as DIR/<name>.npy, float32 / float64")
     return ap.parse_args(argv)
 
 
@@ -161,6 +176,85 @@ def parity_check(cs, data, offsets, num_chunks: int, got, config: str):
         out["result"] = "DIFFERENT: " + str(e)[:300]
     out["check_s"] = round(time.perf_counter() - t, 2)
     return out
+
+
+DUMP_ROWS = 1 << 15             # --dump-outputs: rows of the fixed, seeded sample (halved until the files fit DUMP_LIMIT)
+DUMP_SEED = 1234
+DUMP_LIMIT = 64 << 20
+
+
+def _ranges(off, lens):
+    """Positions [off[i], off[i] + lens[i]) of every row i, concatenated (the child slots / bytes of a list / string column)."""
+    import numpy as np
+    return np.repeat(off[:-1] - (np.cumsum(lens) - lens), lens) + np.arange(int(lens.sum()), dtype=np.int64)
+
+
+def _dump_column(name: str, a, out: dict) -> None:
+    """One Arrow column of the sample as float32 / float64 arrays keyed by its dotted path: every node's validity
+    (`.valid`), list / map / string lengths (`.len`), string bytes (`.bytes`), union type codes (`.type`) and the leaf
+    values.  Null slots count as 0 / empty whatever their buffers hold; a 64-bit integer is written as its (high, low)
+    32-bit halves, which float64 holds exactly.  The types are those the engine produces for the benchmark schemas."""
+    import numpy as np
+    import pyarrow as pa
+    t = a.type
+    valid = a.is_valid().to_numpy(zero_copy_only=False)
+    out[name + ".valid"] = valid.astype(np.float32)
+    if pa.types.is_null(t):
+        return
+    if pa.types.is_struct(t):
+        for i in range(t.num_fields):
+            _dump_column(f"{name}.{t.field(i).name}", a.field(i), out)
+    elif pa.types.is_list(t) or pa.types.is_map(t):
+        off = a.offsets.to_numpy(zero_copy_only=False).astype(np.int64)
+        lens = np.where(valid, np.diff(off), 0)
+        out[name + ".len"] = lens.astype(np.float64)
+        _dump_column(name + ".item", a.values.take(pa.array(_ranges(off, lens), type=pa.int64())), out)
+    elif pa.types.is_union(t) and t.mode == "sparse":
+        codes = a.type_codes.to_numpy(zero_copy_only=False)
+        out[name + ".type"] = codes.astype(np.float32)
+        for i, code in enumerate(t.type_codes):
+            rows = pa.array(np.flatnonzero(codes == code), type=pa.int64())
+            _dump_column(f"{name}.{t.field(i).name}", a.field(i).take(rows), out)
+    elif pa.types.is_string(t) or pa.types.is_binary(t):
+        off = np.frombuffer(a.buffers()[1], np.int32)[a.offset: a.offset + len(a) + 1].astype(np.int64)
+        lens = np.where(valid, np.diff(off), 0)
+        buf = np.frombuffer(a.buffers()[2], np.uint8) if a.buffers()[2] is not None else np.zeros(0, np.uint8)
+        out[name + ".len"] = lens.astype(np.float64)
+        out[name + ".bytes"] = buf[_ranges(off, lens)].astype(np.float32)
+    elif pa.types.is_boolean(t):
+        out[name] = a.fill_null(False).to_numpy(zero_copy_only=False).astype(np.float32)
+    elif pa.types.is_floating(t):
+        out[name] = a.fill_null(0).to_numpy(zero_copy_only=False).astype(np.float64 if t.bit_width == 64 else np.float32)
+    elif pa.types.is_integer(t):
+        v = a.fill_null(0).to_numpy(zero_copy_only=False).astype(np.int64)
+        out[name] = np.stack([v >> 32, v & 0xFFFFFFFF], axis=1).astype(np.float64) if t.bit_width == 64 else v.astype(np.float64)
+    else:
+        raise TypeError(f"--dump-outputs: no flat form for the Arrow type {t} of {name}")
+
+
+def dump_outputs(batches, out_dir: str) -> dict:
+    """--dump-outputs: the RecordBatches one timed step handed its caller, as DIR/<name>.npy.  A fixed, seeded sample of
+    rows (the same rows for the same arguments) of the whole list, every column flattened by _dump_column, plus the
+    rows of each chunk (`chunk_rows`) and the sampled row numbers (`sample_rows`)."""
+    import numpy as np
+    import pyarrow as pa
+    table = pa.Table.from_batches(batches)
+    total = table.num_rows
+    rows = min(total, DUMP_ROWS)
+    while True:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(total, size=rows, replace=False)) if rows < total else np.arange(total)
+        sample = table.take(pa.array(idx, type=pa.int64()))
+        out = {"chunk_rows": np.array([b.num_rows for b in batches], np.float64), "sample_rows": idx.astype(np.float64)}
+        for i, name in enumerate(sample.column_names):
+            _dump_column(name, sample.column(i).combine_chunks(), out)
+        size = sum(v.nbytes for v in out.values())
+        if size <= DUMP_LIMIT or rows <= 1:
+            break
+        rows //= 2
+    os.makedirs(out_dir, exist_ok=True)
+    for key, v in out.items():
+        np.save(os.path.join(out_dir, key + ".npy"), v)
+    return {"dir": out_dir, "rows": int(total), "rows_sampled": int(rows), "arrays": len(out), "bytes": int(size)}
 
 
 def workload_line(workload: str, n: int, chunks: int = 8, kernel: str = "auto", reps: int = 20, parity: bool = True, parity_max: int = 0):
@@ -344,15 +438,15 @@ def cold_start(gen_cfg: str, schema_json: str, n: int = 100_000, num_chunks: int
 def reference_probe():
     """the reference's own numbers need a Rust toolchain on the bench host (cargo bench -p ruhvro --bench
     deserialize, ruhvro/benches/deserialize.rs:55-82; scripts/run_benchmarks.sh).  Probe for one; run the bench when it and the
-    reference tree are both there (never the case on the GPU box: /root/reference does not travel)."""
+    reference tree (named by RUHVRO_REFERENCE_DIR; the repository does not carry it) are both there."""
     import shutil
     import subprocess
     cargo = shutil.which("cargo")
     if not cargo:
         return "unavailable (no cargo on this host)"
-    ref = os.environ.get("RUHVRO_REFERENCE_DIR", "/root/reference")
-    if not os.path.exists(os.path.join(ref, "Cargo.toml")):
-        return f"unavailable (cargo at {cargo}, but no reference tree at {ref})"
+    ref = os.environ.get("RUHVRO_REFERENCE_DIR", "")
+    if not ref or not os.path.exists(os.path.join(ref, "Cargo.toml")):
+        return f"unavailable (cargo at {cargo}, but no reference tree at {ref or '(RUHVRO_REFERENCE_DIR unset)'})"
     try:
         p = subprocess.run([cargo, "bench", "--offline", "-p", "ruhvro", "--bench", "deserialize"], cwd=ref, capture_output=True, text=True, timeout=900)
         tail = [ln for ln in p.stdout.splitlines() if "time:" in ln or "thrpt:" in ln][-12:]
@@ -485,6 +579,11 @@ def run(args, make_step=None, backend="nccl"):
     for _ in range(args.warmup):
         step()
     drain()
+    dump = getattr(args, "dump_outputs", None)
+    if dump:
+        if not hasattr(step, "pipe"):
+            raise SystemExit("bench.py: --dump-outputs needs the GPU step")
+        step.pipe.hold_last = True          # the timed region's final drain keeps the last step's result (freed below)
     sync()
     t0 = time.perf_counter()
     # Kernel durations come from the kernels' own start / stop timestamps (HIP events handed to the launches by the
@@ -515,6 +614,18 @@ def run(args, make_step=None, backend="nccl"):
     sync()
     wall = time.perf_counter() - t0
     wall = rdist.max_over_ranks(wall, dev)
+    run.dumped = None
+    if dump:
+        step.pipe.hold_last = False
+        if step.pipe.held is None:
+            raise SystemExit("bench.py: --dump-outputs needs BENCH_PIPELINE_DEPTH >= 1 (the final drain settles the last step)")
+        call, h = step.pipe.held
+        step.pipe.held = None
+        try:
+            if rank == 0:
+                run.dumped = dump_outputs(call.to_host(h), dump)
+        finally:
+            call.free(h)
 
     # Second timed region (same K steps, same barriers): the steps dealt round-robin to OVERLAP_STREAMS HIP streams.
     # Consecutive steps are independent batches, so the VALU-bound size pass of one runs beside the store-path-bound emit
@@ -522,7 +633,7 @@ def run(args, make_step=None, backend="nccl"):
     # per-kernel duration, so `value` / `roofline` stay with the single-stream region above; this one is reported beside
     # them (`overlapped`).
     run.overlapped = None
-    if use_cuda and hasattr(step, "overlapped") and OVERLAP_STREAMS > 1 and not SYNC_CALLS:
+    if getattr(args, "full", False) and use_cuda and hasattr(step, "overlapped") and OVERLAP_STREAMS > 1 and not SYNC_CALLS:
         ostep = step.overlapped(OVERLAP_STREAMS)
         for _ in range(max(args.warmup, 2 * OVERLAP_STREAMS)):
             ostep()
@@ -566,8 +677,9 @@ class Pipeline:
         import collections
         self.calls = calls if isinstance(calls, (list, tuple)) else [calls]
         self.info, self.ring, self.i = info, collections.deque(), 0
+        self.hold_last, self.held = False, None      # hold_last: drain() settles the last call but leaves it unfreed, as `held`
 
-    def _retire(self):
+    def _retire(self, hold=False):
         call, h, want = self.ring.popleft()
         try:
             call.wait(h, want)          # raises on a malformed record, like the synchronous call
@@ -576,7 +688,10 @@ class Pipeline:
                 st = call.stats.as_dict()
                 self.info["output_bytes"] = call.output_bytes(h)
         finally:
-            call.free(h)
+            if hold:
+                self.held = (call, h)
+            else:
+                call.free(h)
         return st
 
     def submit(self, want_stats):
@@ -593,7 +708,7 @@ class Pipeline:
     def drain(self):
         out = []
         while self.ring:
-            st = self._retire()
+            st = self._retire(hold=self.hold_last and len(self.ring) == 1)
             if st:
                 out.append(st)
         return out
@@ -637,6 +752,7 @@ def gpu_step_factory(gen_cfg, shard, dev, local_rank):
     def step(want_stats=True):
         return pipe.submit(want_stats)
     step.drain = pipe.drain
+    step.pipe = pipe
 
     def rank_step(world, rank=0, nstreams=1):
         """The step rank `rank` of `world` would run on BASELINE config 5 (one list, whole reference chunks per GPU):
@@ -856,8 +972,8 @@ def encode_line(args):
 
 
 def other_configs(local_rank: int = 0, steps: int = 60):
-    """BASELINE configs 2 and 3 (and the full schema at 1M records) and the Arrow -> Avro direction, in the DEFAULT line
-    so that the driver's run carries them: for each, the pipelined step, the synchronous call, the kernels' own times
+    """BASELINE configs 2 and 3 (and the full schema at 1M records) and the Arrow -> Avro direction, in the --full line
+    so that one run carries them: for each, the pipelined step, the synchronous call, the kernels' own times
     (every 4th step carries timestamps) and the same steps dealt to OVERLAP_STREAMS streams.  At 1M records the input
     (16-120 MB) lives in the 256 MB Infinity Cache and a call is 3-4 generations of resident waves: these are
     launch / latency statements, not HBM-bandwidth ones."""
@@ -970,6 +1086,8 @@ def config5_projection(step, ms_per_step_1gpu: float, num_chunks: int, reps: int
 def main(argv=None):
     args = parse_args(argv)
     if args.direction == "encode":
+        if args.dump_outputs:
+            raise SystemExit("bench.py: --dump-outputs writes the decode line's batches (not --direction encode)")
         return encode_main(args)
     global KERNEL, SYNC_CALLS, STREAMS, OVERLAP_STREAMS
     KERNEL = {"auto": 0, "generic": 1, "specialized": 2}[args.kernel]
@@ -1080,11 +1198,18 @@ def main(argv=None):
                    "emit_lds_bytes_per_workgroup": getattr(run, "info", {}).get("lds_bytes", 0),
                    "calls": ("synchronous: every step waits for its own call" if SYNC_CALLS else
                              f"RH_ASYNC on {STREAMS} stream(s), settled {PIPELINE_DEPTH} steps later (rh_device_result_wait), everything inside the timed region"),
-                   "sync_call_ms": run.step.sync_call_ms() if hasattr(run.step, "sync_call_ms") else None,
                    "path_kernel_ms": path_ms,
                    "path_alg_GBps": alg_bytes / (path_ms * 1e-3) / 1e9 if path_ms > 0 else 0.0},
         "roofline": roofline,
     }
+    if getattr(run, "dist", None):
+        out["dist"] = run.dist
+    if run.dumped:
+        print("bench.py: outputs of the last timed step:", json.dumps(run.dumped), file=sys.stderr)
+    if not args.full:           # a plain run: the headline only (set-up, warm-up, the timed steps, --dump-outputs)
+        print(json.dumps(out))
+        return
+    out["config"]["sync_call_ms"] = run.step.sync_call_ms() if hasattr(run.step, "sync_call_ms") else None
     if spec and world == 1 and shard_whole and hasattr(run.step, "other_form_ms"):
         wall2, k2 = run.step.other_form_ms(single_pass=not single)
         p2 = k2["size_kernel_ms"] + k2["scan_kernel_ms"] + k2["emit_kernel_ms"]
@@ -1104,8 +1229,6 @@ def main(argv=None):
                 "path_frac": alg_bytes / (k2["emit_kernel_ms"] * 1e-3) / 1e9 / HBM_PEAK_GBPS,
                 "traffic": tf["hbm_bytes"] if tf else None, "traffic_vs_algorithmic": tf["hbm_bytes"] / alg_bytes if tf else None,
                 "hbm_frac": tf["hbm_bytes"] / (k2["emit_kernel_ms"] * 1e-3) / 1e9 / HBM_PEAK_GBPS if tf else None}
-    if getattr(run, "dist", None):
-        out["dist"] = run.dist
     if getattr(run, "overlapped", None):
         ov = run.overlapped
         total = sum(r["records"] for r in per_rank) * args.steps

@@ -10,7 +10,7 @@
 #   tests:<args>          pytest -m gpu <args>          e.g. tests:tests/test_round5.py   "tests:tests/test_gpu_parity.py -k golden"
 #   notrust               parity core again with RUHVRO_HIP_NO_TRUST=1
 #   smoke                 __graft_entry__.smoke()
-#   bench[:<args>]        bench.py <args> -> bench.json + a short summary
+#   bench[:<args>]        bench.py --full <args> -> bench.json + a short summary
 #   stats[:<workload>]    rocprofv3 --kernel-trace --stats over the bench's single-stream region -> kernel_stats_<workload>.txt
 #   stamp                 FETCH_SIZE / WRITE_SIZE passes (separate) -> hbm_traffic.json stamped with the kernel key, copied to profiles/
 #   stamp_encode          the same for the Arrow -> Avro direction -> encode_hbm_traffic.json
@@ -32,7 +32,7 @@ for step in "$@"; do
     notrust) RUHVRO_HIP_NO_TRUST=1 timeout 900 python -m pytest tests/test_gpu_parity.py tests/test_async_device.py tests/test_single_pass.py -m gpu -q > $OUT/pytest_no_trust.log 2>&1
              echo "pytest NO_TRUST rc=$?" | tee -a $OUT/pytest_no_trust.log; tail -2 $OUT/pytest_no_trust.log;;
     smoke) timeout 300 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1; echo "smoke rc=$?"; tail -1 $OUT/smoke.log;;
-    bench) timeout 1200 python bench.py $arg > $OUT/bench_$n.json 2> $OUT/bench_$n.err; echo "bench rc=$?"; tail -2 $OUT/bench_$n.err
+    bench) timeout 1200 python bench.py --full $arg > $OUT/bench_$n.json 2> $OUT/bench_$n.err; echo "bench rc=$?"; tail -2 $OUT/bench_$n.err
            cp $OUT/bench_$n.json $OUT/bench.json; python scripts/bench_summary.py $OUT/bench_$n.json;;
     stats) W=${arg:-full10m}
            timeout 300 rocprofv3 --kernel-trace --stats -d $OUT/p_stats -o stats -- python bench.py --workload $W --steps 20 --warmup 5 $B > $OUT/p_stats_$W.log 2>&1; echo "stats rc=$?"

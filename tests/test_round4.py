@@ -6,7 +6,8 @@
 * bench.py through a one-rank RCCL group (backend "nccl"): init_process_group(device_id=...), barrier(device_ids=...), the
   MAX all-reduce and the all-gather of pyruhvro_amd/dist.py run for real on one GPU (the reference's only cross-shard
   step is the ordered join of ruhvro/src/deserialize.rs:115-119; ours is stats only);
-* the bench line carries `parity_check` for its own timed configuration;
+* the bench line carries `parity_check` for its own timed configuration (--full); a plain line carries the headline only, and
+  its --dump-outputs arrays are the oracle's;
 * RUHVRO_HIP_NO_TRUST=1 (the emit pass keeps its own bounds / anomaly checks in every tile) produces the same buffers;
 * RUHVRO_HIP_POISON=1 (pooled memory handed out as 0xA5): both directions still produce the oracle's bytes;
 * the CPython boundary resolves "current device" on the calling thread.
@@ -91,10 +92,31 @@ def test_bench_line_through_a_one_rank_rccl_group():
 
 
 def test_bench_line_carries_parity_evidence_for_its_timed_configuration():
-    d = _run_bench(["--steps", "2", "--warmup", "1", "--workload", "full1m", "--no-end-to-end", "--no-other-configs"], {})
+    d = _run_bench(["--steps", "2", "--warmup", "1", "--workload", "full1m", "--full", "--no-end-to-end", "--no-other-configs"], {})
     pc = d["parity_check"]
     assert pc["result"] == "identical" and pc["records"] == 1_000_000 and pc["chunks"] == 8 and pc["buffers"] > 8 * 30
     assert d["cpu_baseline"]["kind"] == "port" and len(d["cpu_baseline"]["sample"]) < 160
+
+
+def test_plain_bench_line_and_its_dumped_outputs(tmp_path):
+    """A plain run: the headline only, --steps timed steps, and --dump-outputs writes what the last timed step produced --
+    the same arrays as the oracle's batches of the same records put through the same dump."""
+    import bench
+    d = _run_bench(["--gpus", "1", "--steps", "5", "--warmup", "2", "--workload", "full1m", "--dump-outputs", str(tmp_path / "gpu")], {})
+    assert d["steps"] == 5 and d["ms_per_step"] > 0 and d["value"] > 0 and d["config"]["records_total"] == 1_000_000
+    for key in ("overlapped", "config5_projection", "cpu_baseline", "parity_check", "end_to_end", "cold_start", "other_configs"):
+        assert key not in d, key
+    data, offsets = fastgen.generate("full", 1_000_000)
+    bench.dump_outputs(c_walker.decode_packed(c_walker.CompiledSchema(SCHEMAS["full"]), data, offsets, 8, threaded=True),
+                       str(tmp_path / "oracle"))
+    files = sorted(os.listdir(tmp_path / "gpu"))
+    assert files == sorted(os.listdir(tmp_path / "oracle")) and "chunk_rows.npy" in files
+    total = 0
+    for f in files:
+        g, e = np.load(tmp_path / "gpu" / f), np.load(tmp_path / "oracle" / f)
+        assert g.dtype in (np.float32, np.float64) and g.dtype == e.dtype and np.array_equal(g, e), f
+        total += g.nbytes
+    assert total <= 64 << 20
 
 
 def test_no_trust_knob_same_buffers():
