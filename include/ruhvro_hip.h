@@ -43,6 +43,21 @@ typedef struct rh_schema rh_schema;
 rh_schema* rh_schema_compile(const char* json, size_t len, char** err);
 void rh_schema_free(rh_schema* s);
 
+/* Column projection (decode only).  A new, independent, immutable rh_schema that decodes the same Avro records into the
+ * top-level columns names[0..n_names) only, in THAT order: every decode entry point then returns exactly what the full
+ * schema's call followed by RecordBatch.select(names) returns -- buffer for buffer, field metadata included -- without
+ * building, copying or exporting the other columns.  A dropped field is still walked (wire order is field order) with the
+ * size walk's checks, so a malformed record raises the full decode's message for the lowest failing record even when
+ * the damaged bytes belong to a dropped field.  Names are distinct top-level field names; a record / union / array / map
+ * column is taken whole or not at all (a dotted path is refused).  NULL + RH_ERR_SCHEMA-style message in *err for an
+ * empty list, an unknown, duplicate or dotted name.  The result has its own size history and its own specialised
+ * kernels (its generated source differs, so does rh_schema_kernel_key) and is accepted by rh_schema_export, rh_decode,
+ * rh_decode_packed, rh_decode_device (RH_ASYNC / RH_SINGLE_PASS / multi-device forms included), rh_schema_prebuild
+ * (decode kernels only), rh_schema_kernels_ready, rh_schema_kernel_source and rh_schema_kernel_key; rh_encode /
+ * rh_encode_device refuse it with RH_ERR_ARGUMENT.  Free it with rh_schema_free; it does not reference `s`.
+ * Added WITHOUT a change of RH_ABI_VERSION (7): a caller discovers it by the presence of the symbol (dlsym). */
+rh_schema* rh_schema_project(const rh_schema* s, const char* const* names, uint32_t n_names, char** err);
+
 /* Arrow schema of the produced batches, exported as a "+s" struct schema whose
  * children are the batch columns (what arrow-rs hands pyarrow at
  * src/lib.rs:70,88 through its pyarrow FFI).  Caller releases out->release. */

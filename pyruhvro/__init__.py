@@ -1,6 +1,7 @@
 """Drop-in module name: ``import pyruhvro`` resolves to the MI355X-native engine.
 
-Same five functions as the reference's PyO3 module (src/lib.rs:150-158)."""
+Same five functions as the reference's PyO3 module (src/lib.rs:150-158); the three decode functions also take the
+keyword-only extension ``columns=[...]`` (decode only those top-level fields)."""
 from pyruhvro_amd import (  # noqa: F401
     deserialize_array,
     deserialize_array_threaded,

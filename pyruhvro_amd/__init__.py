@@ -60,15 +60,27 @@ class _Compiled:
         self.arrow_schema = arrow_schema
 
 
-def _get_schema(schema: str) -> _Compiled:
+def _check_columns(columns):
+    from .cabi import check_columns
+    return check_columns(columns)
+
+
+def _get_schema(schema: str, columns=None) -> _Compiled:
+    """The compiled schema, or -- `columns`: a tuple of distinct top-level field names -- its projection onto those columns
+    (cached by (schema string, columns): a projection is a schema of its own, with its own kernels and size history)."""
     if not isinstance(schema, str):
         raise TypeError("argument 'schema': expected str")
+    columns = _check_columns(columns)         # ValueError before any native work
+    key = schema if columns is None else (schema, columns)
     with _cache_lock:
-        hit = _cache.get(schema)
+        hit = _cache.get(key)
     if hit is not None:
         return hit
     nat = _require_native()
-    cap = nat.compile_schema(schema)          # ValueError on a bad / unsupported schema (src/lib.rs:52)
+    if columns is None:
+        cap = nat.compile_schema(schema)      # ValueError on a bad / unsupported schema (src/lib.rs:52)
+    else:
+        cap = nat.project_schema(_get_schema(schema).capsule, columns)   # ValueError: unknown / dotted name
     addr = nat.export_schema(cap)
     try:
         st = pa.DataType._import_from_c(addr)  # "+s" struct whose fields are the batch columns
@@ -76,12 +88,13 @@ def _get_schema(schema: str) -> _Compiled:
         nat.free_struct(addr)
     comp = _Compiled(cap, pa.schema(list(st)))
     with _cache_lock:
-        return _cache.setdefault(schema, comp)
+        return _cache.setdefault(key, comp)
 
 
-def arrow_schema(schema: str) -> pa.Schema:
-    """Arrow schema the decode produces for this Avro schema (schema_translate.rs:19-37)."""
-    return _get_schema(schema).arrow_schema
+def arrow_schema(schema: str, *, columns=None) -> pa.Schema:
+    """Arrow schema the decode produces for this Avro schema (schema_translate.rs:19-37); `columns`: of the projection
+    onto those top-level fields, in that order."""
+    return _get_schema(schema, columns).arrow_schema
 
 
 KERNEL_AUTO, KERNEL_GENERIC, KERNEL_SPECIALIZED = 0, 1, 2
@@ -134,8 +147,8 @@ def _current_devices():
     return _devices if _devices is not None else _env_devices()
 
 
-def _decode(list_, schema: str, num_chunks: int, want_stats: bool = False, device: int = -1, stream: int = 0):
-    comp = _get_schema(schema)
+def _decode(list_, schema: str, num_chunks: int, want_stats: bool = False, device: int = -1, stream: int = 0, columns=None):
+    comp = _get_schema(schema, columns)
     nat = _require_native()
     if not isinstance(num_chunks, int) or isinstance(num_chunks, bool):
         raise TypeError("argument 'num_chunks': expected int")
@@ -156,25 +169,29 @@ def _decode(list_, schema: str, num_chunks: int, want_stats: bool = False, devic
     return out, stats
 
 
-def deserialize_array(list, schema):  # noqa: A002 - the reference's parameter name
-    """src/lib.rs:56-71 -> ruhvro::deserialize::per_datum_deserialize (deserialize.rs:25-30)."""
-    return _decode(list, schema, 1)[0][0]
+def deserialize_array(list, schema, *, columns=None):  # noqa: A002 - the reference's parameter name
+    """src/lib.rs:56-71 -> ruhvro::deserialize::per_datum_deserialize (deserialize.rs:25-30).
+
+    ``columns`` (keyword only, an extension): decode only these top-level fields, in this order -- the batch equals the
+    full decode's ``.select(columns)`` buffer for buffer; the other columns are neither built nor copied.  A malformed
+    record still raises the full decode's error, whichever field it damages."""
+    return _decode(list, schema, 1, columns=columns)[0][0]
 
 
-def deserialize_array_threaded(list, schema, num_chunks):  # noqa: A002
+def deserialize_array_threaded(list, schema, num_chunks, *, columns=None):  # noqa: A002
     """src/lib.rs:73-89 -> per_datum_deserialize_threaded (deserialize.rs:76-121):
-    ``clamp(num_chunks, 1, max(len(list), 1))`` batches, chunk order preserved."""
-    return _decode(list, schema, num_chunks)[0]
+    ``clamp(num_chunks, 1, max(len(list), 1))`` batches, chunk order preserved.  ``columns``: see deserialize_array."""
+    return _decode(list, schema, num_chunks, columns=columns)[0]
 
 
-def deserialize_array_threaded_spawn(list, schema, num_chunks):  # noqa: A002
+def deserialize_array_threaded_spawn(list, schema, num_chunks, *, columns=None):  # noqa: A002
     """src/lib.rs:108-128 -- same results as deserialize_array_threaded (deserialize.rs:127-170)."""
-    return _decode(list, schema, num_chunks)[0]
+    return _decode(list, schema, num_chunks, columns=columns)[0]
 
 
-def deserialize_array_threaded_with_stats(list, schema, num_chunks, device: int = -1):  # noqa: A002
+def deserialize_array_threaded_with_stats(list, schema, num_chunks, device: int = -1, *, columns=None):  # noqa: A002
     """Extension: also returns the engine's per-stage timings (rh_stats)."""
-    return _decode(list, schema, num_chunks, want_stats=True, device=device)
+    return _decode(list, schema, num_chunks, want_stats=True, device=device, columns=columns)
 
 
 def last_decode_profile():
@@ -184,7 +201,7 @@ def last_decode_profile():
     return _native.last_decode_profile()
 
 
-def deserialize_binary_array(array, schema, num_chunks):
+def deserialize_binary_array(array, schema, num_chunks, *, columns=None):
     """Extension: the same decode for records that already sit in an Arrow
     ``BinaryArray`` / ``LargeBinaryArray`` (one record per element) -- the form the reference packs its
     list into internally (deserialize.rs:90).  Zero-copy on the payload: no per-``bytes`` extraction
@@ -201,7 +218,7 @@ def deserialize_binary_array(array, schema, num_chunks):
         raise TypeError("argument 'num_chunks': expected int")
     if num_chunks < 0:
         raise OverflowError("can't convert negative int to unsigned")
-    _get_schema(schema)                                  # ValueError on a bad / unsupported schema, like every entry point
+    _get_schema(schema, columns)                         # ValueError on a bad / unsupported schema, like every entry point
     n = len(array)
     bufs = array.buffers()
     odt = np.int64 if isinstance(array, pa.LargeBinaryArray) else np.int32
@@ -211,12 +228,12 @@ def deserialize_binary_array(array, schema, num_chunks):
     data = (np.frombuffer(bufs[2], dtype=np.uint8, count=end)[base:] if bufs[2] is not None and end > base
             else np.zeros(1, dtype=np.uint8))
     offsets = (offs.astype(np.uint64) - np.uint64(base)) if n else np.zeros(1, dtype=np.uint64)
-    return cabi.decode_packed(data, offsets, schema, num_chunks, kernel=_kernel_mode, devices=_current_devices())
+    return cabi.decode_packed(data, offsets, schema, num_chunks, kernel=_kernel_mode, devices=_current_devices(), columns=columns)
 
 
 def _encode(data, schema: str, num_chunks: int, want_stats: bool = False, device: int = -1, stream: int = 0):
     import ctypes
-    comp = _get_schema(schema)
+    comp = _get_schema(schema)                 # (always the full schema: projection is decode only)
     nat = _require_native()
     if isinstance(data, pa.RecordBatch):
         sa = data.to_struct_array()
@@ -267,27 +284,27 @@ def device_count() -> int:
     return _require_native().device_count()
 
 
-def deserialize_to_device(records, schema, num_chunks, device: int = -1, stream: int = 0):
+def deserialize_to_device(records, schema, num_chunks, device: int = -1, stream: int = 0, *, columns=None):
     """Extension: the same decode with the Arrow buffers left in HBM, every buffer a DLPack producer
     (``torch.from_dlpack(dec.batches[0].column("created_at").values)`` is an int64 tensor over the engine's memory, no copy).
     See ``pyruhvro_amd.device``."""
     from .device import deserialize_to_device as f
-    return f(records, schema, num_chunks, device=device, stream=stream, kernel=_kernel_mode)
+    return f(records, schema, num_chunks, device=device, stream=stream, kernel=_kernel_mode, columns=columns)
 
 
-def kernels_ready(schema: str, encode: bool = False, timeout_ms: int = 0) -> bool:
+def kernels_ready(schema: str, encode: bool = False, timeout_ms: int = 0, *, columns=None) -> bool:
     """Extension.  A schema this process has not met is decoded by the generic kernels at once while the kernels specialised
     to it compile in the background (the reference's cost of a new schema is a JSON parse, ``src/lib.rs:39-54``; a hiprtc
     compile is seconds).  True when they are there -- the next call runs on them; waits up to ``timeout_ms`` for running
     compile jobs.  Raises ``RuntimeError`` if the compile failed (calls keep working on the generic kernels)."""
-    return bool(_require_native().kernels_ready(_get_schema(schema).capsule, bool(encode), int(timeout_ms)))
+    return bool(_require_native().kernels_ready(_get_schema(schema, columns).capsule, bool(encode), int(timeout_ms)))
 
 
-def prebuild(schema: str) -> bool:
+def prebuild(schema: str, *, columns=None) -> bool:
     """Extension.  Compile this schema's specialised kernels now (all of them, side by side) and wait: for services that
     want their first batch at full speed.  The code objects land in the kernel cache (``RUHVRO_HIP_KERNEL_CACHE`` or
     ``pyruhvro_amd/_kcache``), where later processes find them.  True when nothing had to be compiled."""
-    return bool(_require_native().prebuild(_get_schema(schema).capsule))
+    return bool(_require_native().prebuild(_get_schema(schema, columns).capsule))
 
 
 __all__ = [

@@ -91,6 +91,8 @@ def lib():
         L.rh_schema_compile.restype = C.c_void_p
         L.rh_schema_compile.argtypes = [C.c_char_p, C.c_size_t, C.POINTER(C.c_char_p)]
         L.rh_schema_free.argtypes = [C.c_void_p]
+        L.rh_schema_project.restype = C.c_void_p      # (no ABI version bump: present in every build that has projection)
+        L.rh_schema_project.argtypes = [C.c_void_p, C.POINTER(C.c_char_p), C.c_uint32, C.POINTER(C.c_char_p)]
         L.rh_schema_export.argtypes = [C.c_void_p, C.POINTER(ArrowSchema)]
         L.rh_clamp_chunks.restype = C.c_uint32
         L.rh_clamp_chunks.argtypes = [C.c_uint64, C.c_uint64]
@@ -167,16 +169,42 @@ def _raise(rc: int, err: C.c_char_p):
     raise RuntimeError(msg)
 
 
+def check_columns(columns):
+    """The `columns=` argument of the decode entry points -> None (every column) or a tuple of distinct str.  Raises
+    ValueError naming the offender (empty list, a non-str entry, a duplicate) before any native call; unknown and dotted
+    names are refused by rh_schema_project, which knows the schema."""
+    if columns is None:
+        return None
+    if isinstance(columns, (str, bytes)):
+        raise ValueError(f"columns: expected a list of top-level field names, got {columns!r}")
+    cols = tuple(columns)
+    if not cols:
+        raise ValueError("columns: the projection is empty (name at least one top-level field, or pass None for all)")
+    seen = set()
+    for i, c in enumerate(cols):
+        if not isinstance(c, str):
+            raise ValueError(f"columns: entry {i} ({c!r}) is not a str")
+        if c in seen:
+            raise ValueError(f"columns: duplicate field '{c}'")
+        seen.add(c)
+    return cols
+
+
 class Schema:
-    """Compiled schema handle (rh_schema*) + the pyarrow schema of its batches."""
+    """Compiled schema handle (rh_schema*) + the pyarrow schema of its batches.  `columns`: the projection onto those
+    top-level fields (rh_schema_project), an independent schema with its own kernels and size history."""
 
     _cache: dict = {}
 
-    def __init__(self, schema_json: str):
+    def __init__(self, schema_json: str, columns=None):
         L = lib()
-        raw = schema_json.encode()
         err = C.c_char_p()
-        self.handle = L.rh_schema_compile(raw, len(raw), C.byref(err))
+        if columns is None:
+            raw = schema_json.encode()
+            self.handle = L.rh_schema_compile(raw, len(raw), C.byref(err))
+        else:
+            names = (C.c_char_p * len(columns))(*[c.encode() for c in columns])
+            self.handle = L.rh_schema_project(Schema.get(schema_json).handle, names, len(columns), C.byref(err))
         if not self.handle:
             _raise(RH_ERR_SCHEMA, err)
         cs = ArrowSchema()
@@ -186,10 +214,12 @@ class Schema:
         self.arrow_schema = pa.schema(list(st))
 
     @classmethod
-    def get(cls, schema_json: str) -> "Schema":
-        s = cls._cache.get(schema_json)
+    def get(cls, schema_json: str, columns=None) -> "Schema":
+        columns = check_columns(columns)
+        key = schema_json if columns is None else (schema_json, columns)
+        s = cls._cache.get(key)
         if s is None:
-            s = cls._cache[schema_json] = cls(schema_json)
+            s = cls._cache[key] = cls(schema_json, columns)
         return s
 
 
@@ -203,10 +233,10 @@ RH_SINGLE_PASS = 32  # rh_opts.flags: rh_decode_device prefers the single-pass f
 RH_ASYNC = 8      # rh_opts.flags: rh_decode_device returns once the call is on the stream (rh_device_result_wait settles it)
 
 
-def kernel_source(schema_json: str) -> str:
+def kernel_source(schema_json: str, columns=None) -> str:
     """HIP source of the schema-specialised kernels (rh_schema_kernel_source)."""
     L = lib()
-    p = L.rh_schema_kernel_source(Schema.get(schema_json).handle)
+    p = L.rh_schema_kernel_source(Schema.get(schema_json, columns).handle)
     if not p:
         raise RuntimeError("rh_schema_kernel_source failed")
     try:
@@ -215,10 +245,10 @@ def kernel_source(schema_json: str) -> str:
         L.rh_free_string(p)
 
 
-def kernel_key(schema_json: str, encode: bool = False) -> str:
+def kernel_key(schema_json: str, encode: bool = False, columns=None) -> str:
     """Content hash of the schema's specialised kernel pair (rh_schema_kernel_key): the kernel-cache key."""
     L = lib()
-    p = L.rh_schema_kernel_key(Schema.get(schema_json).handle, 1 if encode else 0)
+    p = L.rh_schema_kernel_key(Schema.get(schema_json, columns).handle, 1 if encode else 0)
     if not p:
         raise RuntimeError("rh_schema_kernel_key failed")
     try:
@@ -239,23 +269,23 @@ def encode_kernel_source(schema_json: str) -> str:
         L.rh_free_string(p)
 
 
-def prebuild(schema_json: str) -> bool:
+def prebuild(schema_json: str, columns=None) -> bool:
     """Compile the schema-specialised kernels into the on-disk kernel cache (hiprtc; no GPU needed).
     Returns True when the code object was already cached."""
     L = lib()
     cached = C.c_int()
     err = C.c_char_p()
-    rc = L.rh_schema_prebuild(Schema.get(schema_json).handle, C.byref(cached), C.byref(err))
+    rc = L.rh_schema_prebuild(Schema.get(schema_json, columns).handle, C.byref(cached), C.byref(err))
     if rc != RH_OK:
         _raise(rc, err)
     return bool(cached.value)
 
 
-def kernels_ready(schema_json: str, encode: bool = False, timeout_ms: int = 0) -> bool:
+def kernels_ready(schema_json: str, encode: bool = False, timeout_ms: int = 0, columns=None) -> bool:
     """rh_schema_kernels_ready: True when the schema's specialised kernels are there (the next call runs on them), False while
     their compile jobs are still running after `timeout_ms` (or nobody asked for them); raises when the compile failed."""
     err = C.c_char_p()
-    rc = lib().rh_schema_kernels_ready(Schema.get(schema_json).handle, 1 if encode else 0, int(timeout_ms), C.byref(err))
+    rc = lib().rh_schema_kernels_ready(Schema.get(schema_json, columns).handle, 1 if encode else 0, int(timeout_ms), C.byref(err))
     if rc < 0:
         _raise(RH_ERR_RUNTIME, err)
     return rc == 1
@@ -269,12 +299,12 @@ def shard_chunks(n: int, num_chunks: int, n_shards: int, shard: int):
 
 
 def decode_packed(data: np.ndarray, offsets: np.ndarray, schema_json: str, num_chunks: int,
-                  device: int = -1, want_stats: bool = False, kernel: int = KERNEL_AUTO, devices=None):
+                  device: int = -1, want_stats: bool = False, kernel: int = KERNEL_AUTO, devices=None, *, columns=None):
     """rh_decode_packed: one contiguous payload + u64 offsets (host memory) -> list[RecordBatch].
     `devices`: shard the chunks over these HIP devices (rh_opts.devices); with want_stats the stats dict then carries
     the per-shard stats under "device_stats"."""
     L = lib()
-    s = Schema.get(schema_json)
+    s = Schema.get(schema_json, columns)
     data = np.ascontiguousarray(data, dtype=np.uint8)
     offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
     n = len(offsets) - 1
@@ -298,11 +328,11 @@ def decode_packed(data: np.ndarray, offsets: np.ndarray, schema_json: str, num_c
 
 
 def decode_slices(ptrs: np.ndarray, lens: np.ndarray, schema_json: str, num_chunks: int,
-                  device: int = -1, want_stats: bool = False, kernel: int = KERNEL_AUTO, devices=None):
+                  device: int = -1, want_stats: bool = False, kernel: int = KERNEL_AUTO, devices=None, *, columns=None):
     """rh_decode: one (pointer, length) pair per record, the form the CPython boundary extracts from list[bytes]
     (u64 addresses / u64 lengths; the caller keeps the pointed-to memory alive) -> list[RecordBatch]."""
     L = lib()
-    s = Schema.get(schema_json)
+    s = Schema.get(schema_json, columns)
     ptrs = np.ascontiguousarray(ptrs, dtype=np.uint64)
     lens = np.ascontiguousarray(lens, dtype=np.uint64)
     n = len(ptrs)
@@ -444,12 +474,13 @@ def encode_device(batch_array_addr: int, batch_schema_addr: int, schema_json: st
 
 def decode_device(d_data: int, d_offsets: int, data_len: int, n: int, schema_json: str, num_chunks: int,
                   device: int = -1, stream: int = 0, want_stats: bool = True, kernel: int = KERNEL_AUTO,
-                  chunk_rows: int = 0, asynchronous: bool = False, two_pass: bool = False, single_pass: bool = False) -> DeviceResult:
+                  chunk_rows: int = 0, asynchronous: bool = False, two_pass: bool = False, single_pass: bool = False,
+                  *, columns=None) -> DeviceResult:
     """rh_decode_device on raw device pointers (e.g. torch tensors' data_ptr()).  chunk_rows: explicit geometry
     for a range of a larger call's chunks (rh_opts.chunk_rows).  asynchronous: RH_ASYNC -- the result is returned
     unsettled (DeviceResult.wait() settles it and fills .stats; every accessor settles implicitly)."""
     L = lib()
-    s = Schema.get(schema_json)
+    s = Schema.get(schema_json, columns)
     out = C.c_void_p()
     st = RhStats()
     err = C.c_char_p()
@@ -472,9 +503,9 @@ class PreparedDeviceDecode:
 
     def __init__(self, d_data: int, d_offsets: int, data_len: int, n: int, schema_json: str, num_chunks: int,
                  device: int = -1, stream: int = 0, kernel: int = KERNEL_AUTO, chunk_rows: int = 0, asynchronous: bool = False,
-                 two_pass: bool = False, single_pass: bool = False):
+                 two_pass: bool = False, single_pass: bool = False, *, columns=None):
         self._L = lib()
-        self._schema = Schema.get(schema_json)
+        self._schema = Schema.get(schema_json, columns)
         self._opts, self._keep = make_opts(device, kernel | (RH_ASYNC if asynchronous else 0) | (RH_TWO_PASS if two_pass else 0) |
                                            (RH_SINGLE_PASS if single_pass else 0), stream, None, chunk_rows)
         self._wait = self._L.rh_device_result_wait

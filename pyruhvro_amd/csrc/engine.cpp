@@ -182,6 +182,27 @@ rh_schema* rh_schema_compile(const char* json, size_t len, char** err) {
   return out;
 }
 
+rh_schema* rh_schema_project(const rh_schema* s, const char* const* names, uint32_t n_names, char** err) {
+  rh_schema* out = nullptr;
+  if (!s || (n_names && !names)) {
+    if (err) *err = dup_msg("rh_schema_project: null argument");
+    return nullptr;
+  }
+  guarded(err, [&] {
+    std::vector<std::string> cols;
+    for (uint32_t i = 0; i < n_names; i++) {
+      if (!names[i]) throw rh::SchemaError("columns: entry " + std::to_string(i) + " is not a string");
+      cols.emplace_back(names[i]);
+    }
+    // from the schema TEXT: the projection is an independent, immutable schema (own size history, own kernels)
+    auto cs = rh::compile_schema_projected(s->cs->json.data(), s->cs->json.size(), cols);
+    out = new rh_schema();
+    out->cs = std::move(cs);
+    return RH_OK;
+  });
+  return out;
+}
+
 void rh_schema_free(rh_schema* s) {
   if (!s) return;
   for (auto& kv : s->dev) {
@@ -234,7 +255,7 @@ char* rh_schema_kernel_source(const rh_schema* s) {
 char* rh_schema_kernel_key(const rh_schema* s, int encode) {
   if (!s) return nullptr;
   try {
-    if (encode && !s->cs->encode_unsupported.empty()) return nullptr;
+    if (encode && (!s->cs->encode_unsupported.empty() || s->cs->projected)) return nullptr;
     const std::string src = encode ? rh::generate_encode_source(*s->cs) : rh::generate_kernel_source(*s->cs);
     return dup_msg(rh::kernel_cache_key(src, encode != 0));
   } catch (...) {
@@ -243,7 +264,7 @@ char* rh_schema_kernel_key(const rh_schema* s, int encode) {
 }
 
 char* rh_schema_encode_kernel_source(const rh_schema* s) {
-  if (!s || !s->cs->encode_unsupported.empty()) return nullptr;
+  if (!s || !s->cs->encode_unsupported.empty() || s->cs->projected) return nullptr;
   try {
     return dup_msg(rh::generate_encode_source(*s->cs));
   } catch (...) {
@@ -262,7 +283,7 @@ int rh_schema_prebuild(const rh_schema* s, int* cached, char** err) {
     const bool fused = env_long("RUHVRO_HIP_PREBUILD_FUSED", 1, 0, 1) != 0;
     const bool ranged = env_long("RUHVRO_HIP_PREBUILD_RANGED", 1, 0, 1) != 0;
     const unsigned parts = (rh::kDecodeParts & ~(fused ? 0u : (1u << rh::KP_FUSED)) & ~(ranged ? 0u : ((1u << rh::KP_SIZE_R) | (1u << rh::KP_EMIT_R)))) |
-                           ((s->cs->encode_unsupported.empty() && !s->cs->wide) ? rh::kEncodeParts : 0u);      // (a wide schema's Arrow -> Avro pair is compiled by its first rh_encode: the encode generator unrolls every column)
+                           ((s->cs->encode_unsupported.empty() && !s->cs->wide && !s->cs->projected) ? rh::kEncodeParts : 0u);      // (a wide schema's Arrow -> Avro pair is compiled by its first rh_encode: the encode generator unrolls every column)
     rh::KernelImage im[rh::KP_COUNT];
     const unsigned started = rh::kernel_images(s->images, *s->cs, parts, rh::CP_BLOCKING, im);
     for (int p = 0; p < rh::KP_COUNT; p++) {
@@ -277,6 +298,10 @@ int rh_schema_prebuild(const rh_schema* s, int* cached, char** err) {
 int rh_schema_kernels_ready(const rh_schema* s, int encode, long timeout_ms, char** err) {
   if (!s) return -1;
   try {
+    if (encode && s->cs->projected) {
+      if (err) *err = dup_msg("a projected schema is decode only");
+      return -1;
+    }
     const unsigned parts = encode ? rh::kEncodeParts : ((1u << rh::KP_SIZE) | (1u << rh::KP_EMIT));
     rh::KernelImage im[rh::KP_COUNT];
     rh::kernel_images(s->images, *s->cs, parts, rh::CP_CACHED_ONLY, im);      // (a first look at the disk cache; starts nothing)

@@ -126,7 +126,7 @@ struct rh_decode_call {
     if (n > 0) {
       emit_lds = lds_bytes;
       if (sk ? launch_module(sk->emit_fn, P, nblocks, (uint32_t)tile, emit_lds, stream, ev.at(3), P.ranged ? nullptr : ev.at(4))
-             : rh_launch_emit(&P, emit_lds, stream, ev.at(3), ev.at(4)))
+             : (cs.projected ? rh_launch_emit_drop : rh_launch_emit)(&P, emit_lds, stream, ev.at(3), ev.at(4)))
         throw HipError("k_emit launch failed");
       if (P.ranged && launch_module(emit_r, P, nblocks + (P.worklist ? rh::kBigFront : 0u), (uint32_t)tile, emit_lds, stream, nullptr, ev.at(4))) throw HipError("k_emit (ranged) launch failed");
     } else {
@@ -372,7 +372,9 @@ struct rh_decode_call {
     P.tileflag = (uint32_t*)(ws.ptr() + o_flag);
     P.lanecnt = (uint32_t*)(ws.ptr() + o_lcnt);
     P.lanecnt32 = (uint32_t*)(ws.ptr() + o_lcnt32);
-    P.worklist = (P.ranged && K > 0 && n > 0) ? (uint32_t*)(ws.ptr() + o_wl) : nullptr;      // (filled by the size kernel: only with a size pass)
+    // (a projection without variable-length output that dropped variable-length fields keeps its size pass: schema.h size_always)
+    const bool size_pass = K > 0 || cs.size_always;
+    P.worklist = (P.ranged && size_pass && n > 0) ? (uint32_t*)(ws.ptr() + o_wl) : nullptr;      // (filled by the size kernel: only with a size pass)
     P.bigmark = P.worklist ? P.worklist + 2 + nblocks : nullptr;
 
     // LDS: fixed part + input window sized from the mean record length (falls back to global reads
@@ -457,18 +459,22 @@ struct rh_decode_call {
     // e3..e4 = k_emit
     if (start_after) HIPCHK(hipStreamWaitEvent(stream, start_after, 0));
     if (try_single(two_sync, ratio_hook)) return;
-    timed_size = n > 0 && K > 0;
+    timed_size = n > 0 && size_pass;
     if (timed_size) {
       if (P.worklist) HIPCHK(hipMemsetAsync(P.worklist, 0, 8ull + 8ull * nblocks, stream));      // the list's length, every tile's mark
 
       // (with the ranged pair: the size kernel's start and the ranged size kernel's stop bracket the pass)
       if (sk ? launch_module(sk->size_fn, P, nblocks, (uint32_t)tile, lds_bytes, stream, ev.at(0), P.ranged ? nullptr : ev.at(1))
-             : rh_launch_size(&P, lds_bytes, stream, ev.at(0), ev.at(1)))
+             : (cs.projected ? rh_launch_size_drop : rh_launch_size)(&P, lds_bytes, stream, ev.at(0), ev.at(1)))
         throw HipError("k_size launch failed");
       if (P.ranged && launch_module(size_r, P, nblocks + (P.worklist ? rh::kBigFront : 0u), (uint32_t)tile, lds_bytes, stream, nullptr, ev.at(1))) throw HipError("k_size (ranged) launch failed");
       if (sized) HIPCHK(hipEventRecord(sized, stream));
       // (the single-submission path scans and lays the arena out in ONE launch, below)
-      if (!fused && rh_launch_scan(&P, stream, ev.at(5), ev.at(2))) throw HipError("k_scan launch failed");
+      if (K == 0) {      // nothing to scan; the emit kernels of a schema without counters do not read the tile flags: all carefully
+        P.all_careful = 1;
+        ev.rec(5, stream);
+        ev.rec(2, stream);
+      } else if (!fused && rh_launch_scan(&P, stream, ev.at(5), ev.at(2))) throw HipError("k_scan launch failed");
     } else {
       // no size pass (no variable-length output): nobody classified the tiles, so the emit kernel walks all of them carefully
       P.all_careful = 1;
@@ -491,7 +497,7 @@ struct rh_decode_call {
       LP.nbuf = nbuf; LP.K = K; LP.ndom = cs.ndom; LP.arena = r.arena.ptr(); LP.capacity = r.arena.b.size;
       LP.bufptr = (void**)dtab.ptr(); LP.bufsize = d_sizes; LP.ctrl = P.first_bad; LP.narrow = sk ? 1u : 0u;
       LP.narrow_rows = narrow_rows;
-      if (timed_size ? rh_launch_scan_layout(&P, &LP, stream, ev.at(5), ev.at(2)) : rh_launch_layout(&LP, stream))
+      if ((timed_size && K > 0) ? rh_launch_scan_layout(&P, &LP, stream, ev.at(5), ev.at(2)) : rh_launch_layout(&LP, stream))
         throw HipError("k_scan / k_layout launch failed");
       launch_tail(true);                           // the layout kernel wrote offsets[0] = 0 itself
       hp.mark("layout+emit_launch");
@@ -505,7 +511,7 @@ struct rh_decode_call {
         if (token == 0) token = next_token.fetch_add(1);
         o_flag_h = align_up(o_null + 4ull * nnodes * k, 8);                 // host layout: head | compact null counts | token
         *(volatile uint32_t*)(hctrl.ptr() + o_flag_h) = 0;
-        if (rh_launch_publish(ctrl->ptr(), hdev, (uint32_t)(o_null / 4), (uint32_t)(nnodes * (int)k), (uint32_t)(o_flag_h / 4), token, null_slots, P.tileflag, (K > 0 && n > 0) ? nblocks : 0u, 8u, stream))
+        if (rh_launch_publish(ctrl->ptr(), hdev, (uint32_t)(o_null / 4), (uint32_t)(nnodes * (int)k), (uint32_t)(o_flag_h / 4), token, null_slots, P.tileflag, timed_size ? nblocks : 0u, 8u, stream))
           throw HipError("k_publish launch failed");
         ctrl->b.clean = true;
         published = true;
@@ -547,7 +553,7 @@ struct rh_decode_call {
       }
       hp.mark("sync");
       check_bad(hctrl.ptr());
-      if (published && K > 0 && n > 0 && !single) {      // the tile statistics rh_k_publish summed (include/ruhvro_hip.h RH_CTR_*_TILES)
+      if (published && timed_size && !single) {      // the tile statistics rh_k_publish summed (include/ruhvro_hip.h RH_CTR_*_TILES)
         const uint32_t* stw = (const uint32_t*)(hctrl.ptr() + 32);
         count(RH_CTR_TILES, nblocks);
         count(RH_CTR_CAREFUL_TILES, stw[0]); count(RH_CTR_OVER_WINDOW_TILES, stw[1]);
@@ -597,7 +603,7 @@ struct rh_decode_call {
       }
     } else {
       count(RH_CTR_TWO_SYNC_CALLS);
-      if (n > 0 && K > 0) {
+      if (timed_size) {
         HIPCHK(hipMemcpyAsync(hctrl.ptr(), ctrl->ptr(), ctrl_bytes, hipMemcpyDeviceToHost, stream));
         HIPCHK(hipStreamSynchronize(stream));
         check_bad(hctrl.ptr());

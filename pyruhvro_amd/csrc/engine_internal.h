@@ -55,6 +55,9 @@ int rh_launch_publish(void* ctrl, void* host, uint32_t head_words, uint32_t null
                       const uint32_t* tileflag, uint32_t nflags, uint32_t stat_word, void* stream);
 int rh_launch_emit(const rh::KParams* P, uint32_t lds_bytes, void* stream, void* start, void* stop);
 int rh_set_max_lds(uint32_t bytes);
+// the generic kernels of a projected schema (kernels.hip: the interpreter with the F_DROP dispatch of walk_drop.h)
+int rh_launch_size_drop(const rh::KParams* P, uint32_t lds_bytes, void* stream, void* start, void* stop);
+int rh_launch_emit_drop(const rh::KParams* P, uint32_t lds_bytes, void* stream, void* start, void* stop);
 uint32_t rh_lds_fixed_bytes(int K, int KL, int tile, int list_depth, int nnodes, int nbuf);
 // Arrow -> Avro kernels (encode.hip)
 int rh_launch_esize(const rh::EParams* P, uint32_t lds_bytes, void* stream);

@@ -29,6 +29,7 @@
 #include "kernel_common.h"
 #include "program.h"
 #include "walk.h"
+#include "walk_drop.h"
 
 namespace rh {
 
@@ -134,7 +135,10 @@ __device__ __forceinline__ Op ld_op(ProgPtr p) {      // (field by field: a stru
   o.buf0 = p->buf0; o.buf1 = p->buf1; o.buf2 = p->buf2; o.node = p->node;
   return o;
 }
-template <bool EMIT, bool CAREFUL, class Ctx, class Src>
+// DROP: the kernels of projected schemas (rh_k_size_p / rh_k_emit_p ...): an op that carries F_DROP -- a field the projection does
+// not keep -- runs counters-only with its counters discarded (walk_drop.h).  The kernels of un-projected schemas are
+// instantiated without the test.
+template <bool EMIT, bool CAREFUL, bool DROP, class Ctx, class Src>
 __device__ __forceinline__ void walk(const KParams& P, const Ctx& c, const Src& src, Lane& L) {
   const ProgPtr prog = reinterpret_cast<ProgPtr>(reinterpret_cast<uintptr_t>(P.prog));
   int pc = 0;
@@ -148,6 +152,13 @@ __device__ __forceinline__ void walk(const KParams& P, const Ctx& c, const Src& 
     if (op.code == OP_END) return;                          // (the last op of a program: nothing is read behind it)
     int npc = op.code == OP_LIST_TAIL ? op.b : pc + 1;      // LIST_TAIL goes back to its LIST_NEXT
     nxt = ld_op(prog + npc);
+    if constexpr (DROP) {
+      if (op.flags & F_DROP) {
+        if (!run_dropped<EMIT, CAREFUL>(c, src, L, op)) { npc = op.b; nxt = ld_op(prog + npc); }
+        pc = npc;
+        continue;
+      }
+    }
     switch (op.code) {
       case OP_FIXED:
         if constexpr (CAREFUL) h_fixed<EMIT, true>(c, src, L, op);
@@ -233,16 +244,16 @@ extern "C" uint32_t rh_lds_fixed_bytes(int K, int KL, int tile, int list_depth, 
 
 // fits: the tile's window is staged in LDS; cursors become LDS byte addresses (walk.h LdsAbsSrc).  A tile past the window is
 // walked carefully, straight from global memory (this form has no ranges: spec_body.h ranged_tile is the specialised kernels').
-template <bool EMIT, bool CAREFUL, int T>
+template <bool EMIT, bool CAREFUL, bool DROP, int T>
 __device__ __forceinline__ void run_walk(const KParams& P, const ICtx<T>& c, const Smem& s, Lane& L, bool fits, uint64_t wb16) {
   if (fits) {
     const uint32_t wa = (uint32_t)(uintptr_t)(RH_LDS uint8_t*)s.win;
     L.cur += wa; L.end += wa;
     LdsAbsSrc src;
-    walk<EMIT, CAREFUL>(P, c, src, L);
+    walk<EMIT, CAREFUL, DROP>(P, c, src, L);
   } else {
     GlobalSrc src{P.data + wb16, P.data_len - wb16};
-    walk<EMIT, true>(P, c, src, L);
+    walk<EMIT, true, DROP>(P, c, src, L);
   }
 }
 
@@ -259,7 +270,7 @@ __device__ __forceinline__ ICtx<T> make_ctx(const KParams& P, const Smem& s, con
 // k_size.  T = records (= threads) per tile: 256, or 64 for a wide schema (program.h kWideTile: one wavefront per tile, so that
 // the byte counters of domain-0 columns are wave counters with no per-lane storage -- ICtx::wave_total / wave_offset)
 // --------------------------------------------------------------------------
-template <int T>
+template <int T, bool DROP = false>
 __device__ __forceinline__ void k_size_body(const KParams& P) {
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
   constexpr int NW = T / 64;
@@ -281,17 +292,17 @@ __device__ __forceinline__ void k_size_body(const KParams& P) {
   uint32_t tflag = fits ? 0u : (uint32_t)(TF_OVER_WINDOW | TF_CAREFUL);
   if (fits) {
     // the fast walk; a wavefront with a record outside the fast wire forms (or malformed) walks again, carefully
-    run_walk<false, false>(P, c, s, L, true, wb16);
+    run_walk<false, false, DROP>(P, c, s, L, true, wb16);
     L.redo = L.redo || L.cur > L.end;
     if (__any(L.redo)) {
       tflag |= (uint32_t)(TF_CAREFUL | TF_REWALK_ONE);
       for (int k = 0; k < P.KL; k++) s.cnt[k * T + tid] = 0;
       for (int d = 0; d < P.list_depth; d++) s.rem[d * T + tid] = 0;
       lane_init(L, P, g, wb16, tid);
-      run_walk<false, true>(P, c, s, L, true, wb16);
+      run_walk<false, true, DROP>(P, c, s, L, true, wb16);
     }
   } else {
-    run_walk<false, true>(P, c, s, L, false, wb16);
+    run_walk<false, true, DROP>(P, c, s, L, false, wb16);
   }
   if (lane == 0 && tflag) { atomicOr(&s.misc[2], tflag & ~(uint32_t)TF_REWALK_ONE); if (tflag & (uint32_t)TF_REWALK_ONE) atomicAdd(&s.misc[2], (uint32_t)TF_REWALK_ONE); }
 
@@ -313,6 +324,8 @@ __device__ __forceinline__ void k_size_body(const KParams& P) {
 }
 extern "C" __global__ void __launch_bounds__(kBlock) rh_k_size(KParams P) { k_size_body<kBlock>(P); }
 extern "C" __global__ void __launch_bounds__(kWideTile) rh_k_size_w(KParams P) { k_size_body<kWideTile>(P); }
+extern "C" __global__ void __launch_bounds__(kBlock) rh_k_size_p(KParams P) { k_size_body<kBlock, true>(P); }      // projected schemas
+extern "C" __global__ void __launch_bounds__(kWideTile) rh_k_size_wp(KParams P) { k_size_body<kWideTile, true>(P); }
 
 // --------------------------------------------------------------------------
 // k_scan: one workgroup per (counter, chunk)
@@ -549,7 +562,7 @@ extern "C" __global__ void __launch_bounds__(kBlock) rh_k_init(void* const* bufp
 // --------------------------------------------------------------------------
 // k_emit
 // --------------------------------------------------------------------------
-template <int T>
+template <int T, bool DROP = false>
 __device__ __forceinline__ void k_emit_body(const KParams& P) {
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
   constexpr int NW = T / 64;
@@ -607,9 +620,9 @@ __device__ __forceinline__ void k_emit_body(const KParams& P) {
   lane_init(L, P, g, wb16, tid);
   if (L.live && (we - wb16) > 0xFFFFFFF0ull) L.err = E_EOB;
   if (careful) {
-    run_walk<true, true>(P, c, s, L, fits, wb16);
+    run_walk<true, true, DROP>(P, c, s, L, fits, wb16);
   } else {
-    run_walk<true, false>(P, c, s, L, true, wb16);     // (trusted: the size pass met no anomaly in this tile)
+    run_walk<true, false, DROP>(P, c, s, L, true, wb16);     // (trusted: the size pass met no anomaly in this tile)
     if (L.redo) L.err = E_INTERNAL;
   }
 
@@ -621,6 +634,8 @@ __device__ __forceinline__ void k_emit_body(const KParams& P) {
 }
 extern "C" __global__ void __launch_bounds__(kBlock) rh_k_emit(KParams P) { k_emit_body<kBlock>(P); }
 extern "C" __global__ void __launch_bounds__(kWideTile) rh_k_emit_w(KParams P) { k_emit_body<kWideTile>(P); }
+extern "C" __global__ void __launch_bounds__(kBlock) rh_k_emit_p(KParams P) { k_emit_body<kBlock, true>(P); }      // projected schemas
+extern "C" __global__ void __launch_bounds__(kWideTile) rh_k_emit_wp(KParams P) { k_emit_body<kWideTile, true>(P); }
 
 }  // namespace rh
 
@@ -677,9 +692,27 @@ extern "C" int rh_launch_emit(const rh::KParams* P, uint32_t lds_bytes, void* st
                         (hipEvent_t)stop, 0, *P);
   return (int)hipGetLastError();
 }
+extern "C" int rh_launch_size_drop(const rh::KParams* P, uint32_t lds_bytes, void* stream, void* start, void* stop) {
+  (void)hipGetLastError();
+  if (P->tile == (uint32_t)rh::kWideTile)
+    hipExtLaunchKernelGGL(rh::rh_k_size_wp, dim3(P->nblocks), dim3(rh::kWideTile), lds_bytes, (hipStream_t)stream, (hipEvent_t)start, (hipEvent_t)stop, 0, *P);
+  else
+    hipExtLaunchKernelGGL(rh::rh_k_size_p, dim3(P->nblocks), dim3(rh::kBlock), lds_bytes, (hipStream_t)stream, (hipEvent_t)start, (hipEvent_t)stop, 0, *P);
+  return (int)hipGetLastError();
+}
+extern "C" int rh_launch_emit_drop(const rh::KParams* P, uint32_t lds_bytes, void* stream, void* start, void* stop) {
+  (void)hipGetLastError();
+  if (P->tile == (uint32_t)rh::kWideTile)
+    hipExtLaunchKernelGGL(rh::rh_k_emit_wp, dim3(P->nblocks), dim3(rh::kWideTile), lds_bytes, (hipStream_t)stream, (hipEvent_t)start, (hipEvent_t)stop, 0, *P);
+  else
+    hipExtLaunchKernelGGL(rh::rh_k_emit_p, dim3(P->nblocks), dim3(rh::kBlock), lds_bytes, (hipStream_t)stream, (hipEvent_t)start, (hipEvent_t)stop, 0, *P);
+  return (int)hipGetLastError();
+}
 extern "C" int rh_set_max_lds(uint32_t bytes) {
   for (const void* f : {reinterpret_cast<const void*>(rh::rh_k_size), reinterpret_cast<const void*>(rh::rh_k_emit),
-                        reinterpret_cast<const void*>(rh::rh_k_size_w), reinterpret_cast<const void*>(rh::rh_k_emit_w)}) {
+                        reinterpret_cast<const void*>(rh::rh_k_size_w), reinterpret_cast<const void*>(rh::rh_k_emit_w),
+                        reinterpret_cast<const void*>(rh::rh_k_size_p), reinterpret_cast<const void*>(rh::rh_k_emit_p),
+                        reinterpret_cast<const void*>(rh::rh_k_size_wp), reinterpret_cast<const void*>(rh::rh_k_emit_wp)}) {
     const int e = (int)hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
     if (e) return e;
   }

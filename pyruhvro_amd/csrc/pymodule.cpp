@@ -57,6 +57,34 @@ rh_schema* get_schema(PyObject* cap) {
   return (rh_schema*)PyCapsule_GetPointer(cap, kCapsule);
 }
 
+// project_schema(capsule, names: sequence of str) -> capsule of the projected schema (rh_schema_project)
+PyObject* py_project_schema(PyObject*, PyObject* args) {
+  PyObject* cap;
+  PyObject* names;
+  if (!PyArg_ParseTuple(args, "OO", &cap, &names)) return nullptr;
+  rh_schema* s = get_schema(cap);
+  if (!s) return nullptr;
+  PyObject* seq = PySequence_Fast(names, "columns: expected a sequence of field names");
+  if (!seq) return nullptr;
+  const Py_ssize_t n = PySequence_Fast_GET_SIZE(seq);
+  std::vector<const char*> ptrs((size_t)n, nullptr);
+  for (Py_ssize_t i = 0; i < n; i++) {
+    PyObject* it = PySequence_Fast_GET_ITEM(seq, i);
+    if (!PyUnicode_Check(it)) {
+      Py_DECREF(seq);
+      PyErr_Format(PyExc_ValueError, "columns: entry %zd is not a str", i);
+      return nullptr;
+    }
+    ptrs[(size_t)i] = PyUnicode_AsUTF8(it);      // (owned by the str object, alive while `seq` is)
+    if (!ptrs[(size_t)i]) { Py_DECREF(seq); return nullptr; }
+  }
+  char* err = nullptr;
+  rh_schema* h = rh_schema_project(s, ptrs.data(), (uint32_t)n, &err);
+  Py_DECREF(seq);
+  if (!h) return raise_from(RH_ERR_SCHEMA, err);
+  return PyCapsule_New(h, kCapsule, capsule_free);
+}
+
 PyObject* py_schema_ptr(PyObject*, PyObject* args) {
   PyObject* cap;
   if (!PyArg_ParseTuple(args, "O", &cap)) return nullptr;
@@ -556,6 +584,7 @@ PyObject* py_last_decode_profile(PyObject*, PyObject*) {
 
 PyMethodDef methods[] = {
     {"compile_schema", py_compile_schema, METH_VARARGS, "compile_schema(json) -> schema capsule"},
+    {"project_schema", py_project_schema, METH_VARARGS, "project_schema(capsule, names) -> capsule of the schema projected onto those top-level columns"},
     {"schema_ptr", py_schema_ptr, METH_VARARGS, "schema_ptr(capsule) -> int (rh_schema*)"},
     {"export_schema", py_export_schema, METH_VARARGS, "export_schema(capsule) -> address of ArrowSchema"},
     {"decode", py_decode, METH_VARARGS, "decode(capsule, list, num_chunks, device=-1, stream=0, want_stats=False, kernel=0, devices=None)"},

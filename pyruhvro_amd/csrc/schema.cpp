@@ -1,11 +1,13 @@
 // See schema.h.  Host only (no HIP).
 #include "schema.h"
+#include <algorithm>
 #include <cmath>
 
 #include <map>
 #include <set>
 
 #include "json.hpp"
+#include "walk_drop.h"
 
 namespace rh {
 namespace {
@@ -508,6 +510,36 @@ struct Builder {
     return id;
   }
 
+  // A top-level field the projection does not keep: its ops, built on the side and appended without buffers, node, counter
+  // or child row domain (walk_drop.h F_DROP).  The walk still nests as deep as the field does.
+  bool dropped_varlen = false;        // a dropped field with a variable-length wire form (string / bytes / array / map)
+  void drop(const AvroType& t, const Ctx& cx) {
+    CompiledSchema tmp;
+    Builder tb{tmp};
+    tb.build(t, false, false, cx);
+    const int32_t pc0 = (int32_t)cs.prog.size(), sym0 = (int32_t)cs.sym_off.size();
+    const uint32_t sd0 = (uint32_t)cs.sym_data.size();
+    for (Op o : tmp.prog) {
+      switch (o.code) {
+        case OP_STRING: o.a = 0; dropped_varlen = true; break;
+        case OP_ENUM: o.a = 0; o.b += sym0; break;               // (the size walk still range-checks the index: c = #symbols)
+        case OP_BIN: dropped_varlen = dropped_varlen || o.a == BN_DEC_BYTES || o.a == BN_UUID_STR; break;
+        case OP_LIST_BEGIN: case OP_LIST_NEXT: case OP_LIST_TAIL: o.a = 1; o.b += pc0; dropped_varlen = true; break;
+        case OP_LIST_END: o.a = 1; break;
+        default: break;
+      }
+      if (o.code != OP_LIST_NEXT) o.buf2 = -1;                   // (LIST_NEXT: min wire bytes per item, the trip-count clamp)
+      o.buf0 = -1; o.buf1 = -1; o.node = -1; o.dom = 0;
+      o.flags |= F_DROP;
+      push(o);
+    }
+    for (uint32_t v : tmp.sym_off) cs.sym_off.push_back(v + sd0);
+    cs.sym_data.insert(cs.sym_data.end(), tmp.sym_data.begin(), tmp.sym_data.end());
+    cs.list_depth = std::max(cs.list_depth, tmp.list_depth);
+    cs.max_nest = std::max(cs.max_nest, tmp.max_nest);
+    cs.max_union_depth = std::max(cs.max_union_depth, tmp.max_union_depth);
+  }
+
   // make_decoder / make_nullable_decoder / make_union_decoder
   int build(const AvroType& t, bool nullable, bool null_first, Ctx cx) {
     if (cx.nest > kMaxNest) throw SchemaError("schema nesting too deep for the GPU decoder");
@@ -673,9 +705,8 @@ struct Builder {
   }
 };
 
-}  // namespace
-
-std::unique_ptr<CompiledSchema> compile_schema(const char* text, size_t len) {
+// `cols` == nullptr: every column
+std::unique_ptr<CompiledSchema> compile_impl(const char* text, size_t len, const std::vector<std::string>* cols) {
   auto cs = std::make_unique<CompiledSchema>();
   cs->json.assign(text, len);
   Value j;
@@ -698,14 +729,52 @@ std::unique_ptr<CompiledSchema> compile_schema(const char* text, size_t len) {
   cs->arrow.format = "+s";
   cs->arrow.name = "";
   cs->arrow.nullable = false;
-  for (auto& f : top.fields) {
+  std::vector<int> keep_at(top.fields.size(), -1);      // field -> its place in the projection, -1 = dropped
+  if (cols) {
+    if (cols->empty()) throw SchemaError("columns: the projection is empty (name at least one top-level field)");
+    for (size_t c = 0; c < cols->size(); c++) {
+      const std::string& name = (*cols)[c];
+      size_t fi = 0;
+      while (fi < top.fields.size() && top.fields[fi].name != name) fi++;
+      if (fi == top.fields.size()) {
+        if (name.find('.') != std::string::npos)
+          throw SchemaError("columns: '" + name + "' is a dotted path: only top-level fields can be selected, a nested "
+                            "record / union / array / map column is taken whole or not at all");
+        throw SchemaError("columns: unknown top-level field '" + name + "'");
+      }
+      if (keep_at[fi] >= 0) throw SchemaError("columns: duplicate field '" + name + "'");
+      keep_at[fi] = (int)c;
+    }
+    cs->projected = true;
+    cs->columns = *cols;
+    cs->arrow.children.resize(cols->size());
+  }
+  for (size_t fi = 0; fi < top.fields.size(); fi++) {
+    auto& f = top.fields[fi];
+    if (cols && keep_at[fi] < 0) continue;
     auto props = external_props(*f.type);
-    cs->arrow.children.push_back(to_field(*f.type, &f.name, false, &props));
+    ArrowField af = to_field(*f.type, &f.name, false, &props);
+    if (cols) cs->arrow.children[(size_t)keep_at[fi]] = std::move(af);
+    else cs->arrow.children.push_back(std::move(af));
   }
 
   Builder b{*cs};
   Builder::Ctx cx{0, false, 0, 0, 0};
-  b.build(top, false, false, cx);
+  if (!cols) {
+    b.build(top, false, false, cx);
+  } else {
+    // the top-level RecordDecoder (Builder::build AV_RECORD, not nullable) with the dropped fields walked, not built
+    if (top.fields.empty()) throw SchemaError("RecordDecoder produced a record with 0 fields");
+    const int id = b.new_node(NK_RECORD);
+    Builder::Ctx cc = cx;
+    cc.nest++;
+    std::vector<int> kids(cols->size(), -1);
+    for (size_t fi = 0; fi < top.fields.size(); fi++) {
+      if (keep_at[fi] >= 0) kids[(size_t)keep_at[fi]] = b.build(*top.fields[fi].type, false, false, cc);
+      else b.drop(*top.fields[fi].type, cc);
+    }
+    cs->nodes[(size_t)id].children = kids;
+  }
   cs->prog.push_back(Builder::mk(OP_END));
 
   // counters: row domains first (domain d -> counter d-1), then the string byte columns.
@@ -742,7 +811,16 @@ std::unique_ptr<CompiledSchema> compile_schema(const char* text, size_t len) {
   if (cs->sym_off.empty()) cs->sym_off.push_back(0);
   if (cs->sym_data.empty()) cs->sym_data.push_back(0);
   cs->min_record_bytes = Builder::min_bytes(top);
+  cs->size_always = cs->projected && cs->K == 0 && b.dropped_varlen;
   return cs;
+}
+
+}  // namespace
+
+std::unique_ptr<CompiledSchema> compile_schema(const char* text, size_t len) { return compile_impl(text, len, nullptr); }
+
+std::unique_ptr<CompiledSchema> compile_schema_projected(const char* text, size_t len, const std::vector<std::string>& columns) {
+  return compile_impl(text, len, &columns);
 }
 
 }  // namespace rh

@@ -109,9 +109,22 @@ struct CompiledSchema {
   uint32_t min_record_bytes = 0;
   uint32_t max_row_bytes = 16;      // widest fixed-width value of one row (bounds the 32-bit in-buffer offsets of the specialised kernels)
   std::string encode_unsupported;   // non-empty: why rh_encode does not take this schema (no such schema today)
+  // Column projection (compile_schema_projected): `prog` still walks every field of the full schema, but the ops of the
+  // fields that were not asked for carry F_DROP (walk_drop.h) and everything else above -- nodes, bufs, counters, row
+  // domains, `arrow` -- describes the kept columns only, in the order asked for.
+  bool projected = false;
+  std::vector<std::string> columns; // the projection, as asked for
+  // K == 0 and a dropped field has a variable-length wire form: tiles past the LDS window are the ordinary case (a few
+  // hundred bytes of dropped strings per record), so the call keeps its size pass -- it classifies the tiles and hands
+  // those past the window to the ranged kernels (LF_NEED_RANGED) -- although nothing has to be sized
+  bool size_always = false;
 };
 
 // Throws SchemaError.  `json` need not be NUL-terminated.
 std::unique_ptr<CompiledSchema> compile_schema(const char* json, size_t len);
+// The same schema decoded into the top-level columns `columns` only (distinct field names of the top-level record, any
+// order: the batch has them in that order).  Throws SchemaError naming the offender for an empty list, a duplicate, an
+// unknown name or a dotted path.
+std::unique_ptr<CompiledSchema> compile_schema_projected(const char* json, size_t len, const std::vector<std::string>& columns);
 
 }  // namespace rh

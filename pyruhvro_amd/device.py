@@ -296,18 +296,19 @@ def _pack(records) -> tuple:
     return np.frombuffer(b"".join(records), dtype=np.uint8), offs
 
 
-def deserialize_to_device(records, schema: str, num_chunks: int, device: int = -1, stream: int = 0, kernel: int = 0) -> DeviceDecode:
+def deserialize_to_device(records, schema: str, num_chunks: int, device: int = -1, stream: int = 0, kernel: int = 0, *, columns=None) -> DeviceDecode:
     """Extension.  Decode like ``deserialize_array_threaded(records, schema, num_chunks)`` but leave the Arrow
     buffers in HBM.  ``records``: a list of ``bytes``, a pyarrow ``BinaryArray`` / ``LargeBinaryArray`` (packed on the host and
     uploaded once), or a pair ``(data, offsets)`` of device arrays that already hold the packed payload and its n + 1 uint64
     offsets (anything with ``data_ptr()`` -- torch tensors -- or raw integer addresses; ``data`` 16-byte aligned with 64 readable
     bytes of slack).  ``stream``: the HIP stream to launch on (e.g. ``torch.cuda.current_stream().cuda_stream``).
+    ``columns``: only these top-level fields, in this order (the other columns get no device buffers at all).
     Errors are the reference's: ``ValueError`` with its message for a malformed datum or an unsupported schema."""
     if not isinstance(num_chunks, int) or isinstance(num_chunks, bool):
         raise TypeError("argument 'num_chunks': expected int")
     if num_chunks < 0:
         raise OverflowError("can't convert negative int to unsigned")
-    s = cabi.Schema.get(schema)
+    s = cabi.Schema.get(schema, columns)
     keep = []
     if isinstance(records, tuple) and len(records) == 2 and not isinstance(records[0], (bytes, bytearray)):
         d_data, d_off = records
@@ -329,7 +330,7 @@ def deserialize_to_device(records, schema: str, num_chunks: int, device: int = -
         p_data, p_off = md.ptr.value, mo.ptr.value
         keep = [md, mo]
     try:
-        r = cabi.decode_device(p_data, p_off, data_len, n, schema, num_chunks, device=device, stream=stream, kernel=kernel)
+        r = cabi.decode_device(p_data, p_off, data_len, n, schema, num_chunks, device=device, stream=stream, kernel=kernel, columns=columns)
     finally:
         for k in keep:
             if isinstance(k, _DevMem):

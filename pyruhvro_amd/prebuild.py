@@ -12,10 +12,13 @@ from concurrent.futures import ProcessPoolExecutor
 from typing import Iterable, List, Tuple
 
 
-def _one(schema_json: str) -> Tuple[bool, str]:
+def _one(item) -> Tuple[bool, str]:
+    """`item`: a schema string, or (schema string, columns) for the kernels of a projection."""
     from pyruhvro_amd import cabi
     try:
-        return cabi.prebuild(schema_json), ""
+        if isinstance(item, tuple):
+            return cabi.prebuild(item[0], columns=item[1]), ""
+        return cabi.prebuild(item), ""
     except Exception as e:  # noqa: BLE001 - reported to the caller
         return False, str(e)
 
@@ -27,7 +30,7 @@ def _cache_dir() -> str:
 def _marker(schemas: List[str]) -> str:
     import hashlib
     variant = os.environ.get("RUHVRO_HIP_VARIANT", "")      # staged kernel variants have their own code objects
-    h = hashlib.sha1(("\0".join(sorted(schemas)) + "\1" + variant).encode()).hexdigest()[:16]
+    h = hashlib.sha1(("\0".join(sorted(s if isinstance(s, str) else repr(s) for s in schemas)) + "\1" + variant).encode()).hexdigest()[:16]
     return os.path.join(_cache_dir(), f"warm_{h}.ok")
 
 

@@ -64,6 +64,16 @@ def known_schemas() -> List[str]:
 
 
 
+def known_projections() -> list:
+    """(schema, columns) pairs whose projected kernels (`columns=`: rh_schema_project) the GPU tests and
+    scripts/projection_bench.py decode with: prebuilt by this script next to the schemas above."""
+    from avrogen.schemas import SCHEMAS
+    import test_projection
+    out = [(s, tuple(c)) for s, c in test_projection.projection_cases()]
+    out += [(SCHEMAS["full"], c) for c in (("created_at", "age"), ("name", "created_at", "class"), ("emails", "phone_numbers"))]
+    return list(dict.fromkeys(out))
+
+
 def single_pass_schemas() -> List[str]:
     """The schemas whose single-pass kernel (rh_spec_fused) a bench line or a test runs: the only ones build() compiles it for --
     it is the most expensive of a schema's five kernels and opt-in; every other schema gets it on first request."""
@@ -79,6 +89,7 @@ if __name__ == "__main__":
     errs = prebuild_many(with_fused, verbose=True)
     os.environ["RUHVRO_HIP_PREBUILD_FUSED"] = "0"
     errs += prebuild_many(rest, verbose=True)
+    errs += prebuild_many(known_projections(), verbose=True)      # (without their single-pass kernel: compiled on first request)
     if not errs:
         from pyruhvro_amd.prebuild import mark_warm
         mark_warm(known_schemas())
