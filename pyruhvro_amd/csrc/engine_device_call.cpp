@@ -243,7 +243,7 @@ struct rh_decode_call {
       if (token == 0) token = next_token.fetch_add(1);
       o_flag_h = align_up(o_null + 4ull * nnodes * k, 8);
       *(volatile uint32_t*)(hctrl.ptr() + o_flag_h) = 0;
-      if (rh_launch_publish(ctrl->ptr(), hdev, (uint32_t)(o_null / 4), (uint32_t)(nnodes * (int)k), (uint32_t)(o_flag_h / 4), token, null_slots, P.tileflag, 0u /* no size pass: nobody wrote the tile flags */, 8u, stream))
+      if (rh_launch_publish(ctrl->ptr(), hdev, (uint32_t)(o_null / 4), (uint32_t)(nnodes * (int)k), (uint32_t)(o_flag_h / 4), token, null_slots, stream))
         throw HipError("k_publish launch failed");
       ctrl->b.clean = true;
       published = true;
@@ -306,7 +306,7 @@ struct rh_decode_call {
       else if (mode == RH_KERNEL_SPECIALIZED) throw HipError("specialised kernel unavailable: " + k0.why);
     }
     // The ranged pair behind the size / emit kernels (spec_body.h ranged_tile): while the schema's recent calls met tiles past the
-    // LDS window (rh_schema::ranged_calls, fed by rh_k_publish's tile statistics), or when the caller insists on the specialised
+    // LDS window (rh_schema::ranged_calls, fed by the call's tile statistics), or when the caller insists on the specialised
     // kernels.  A call that meets such tiles without it takes the fallback (the careful walk from global memory) and, large enough,
     // starts the pair's compile in the background.  RUHVRO_HIP_RANGED=0 / 1: never / always (A/B, tests).
     if (sk) {
@@ -332,7 +332,7 @@ struct rh_decode_call {
 
     // ---- control block: [first_bad u64 | layout flag, ticket | arena bytes | pad][totals u64 K*k][nullcount u32 nnodes*k*null_slots]
     //      workspace: errinfo | blocksum | blockbase | tileflag | lanecnt
-    o_tot = 48;      // control words first (program.h): first_bad, layout flag, arena bytes used, pad; words 8..11 = the tile statistics rh_k_publish sums
+    o_tot = 48;      // control words first (program.h): first_bad, layout flag, arena bytes used, pad; words 8..11 = the tile statistics (summed by rh_k_scan_layout / rh_k_tile_stats, kernels.hip)
     o_tick = o_tot + 8ull * K * k;                    // [k] tile tickets of the single-pass form (zero like the rest of the block)
     o_null = align_up(o_tick + 4ull * k, 16);
     null_slots = rh::null_slots_for(k);
@@ -497,6 +497,8 @@ struct rh_decode_call {
       LP.nbuf = nbuf; LP.K = K; LP.ndom = cs.ndom; LP.arena = r.arena.ptr(); LP.capacity = r.arena.b.size;
       LP.bufptr = (void**)dtab.ptr(); LP.bufsize = d_sizes; LP.ctrl = P.first_bad; LP.narrow = sk ? 1u : 0u;
       LP.narrow_rows = narrow_rows;
+      // (the tile statistics are summed by the scan launch; a size pass with nothing to scan gets a small launch of its own)
+      if (timed_size && K == 0 && rh_launch_tile_stats(ctrl->ptr(), P.tileflag, nblocks, stream)) throw HipError("k_tile_stats launch failed");
       if ((timed_size && K > 0) ? rh_launch_scan_layout(&P, &LP, stream, ev.at(5), ev.at(2)) : rh_launch_layout(&LP, stream))
         throw HipError("k_scan / k_layout launch failed");
       launch_tail(true);                           // the layout kernel wrote offsets[0] = 0 itself
@@ -511,7 +513,7 @@ struct rh_decode_call {
         if (token == 0) token = next_token.fetch_add(1);
         o_flag_h = align_up(o_null + 4ull * nnodes * k, 8);                 // host layout: head | compact null counts | token
         *(volatile uint32_t*)(hctrl.ptr() + o_flag_h) = 0;
-        if (rh_launch_publish(ctrl->ptr(), hdev, (uint32_t)(o_null / 4), (uint32_t)(nnodes * (int)k), (uint32_t)(o_flag_h / 4), token, null_slots, P.tileflag, timed_size ? nblocks : 0u, 8u, stream))
+        if (rh_launch_publish(ctrl->ptr(), hdev, (uint32_t)(o_null / 4), (uint32_t)(nnodes * (int)k), (uint32_t)(o_flag_h / 4), token, null_slots, stream))
           throw HipError("k_publish launch failed");
         ctrl->b.clean = true;
         published = true;
@@ -553,7 +555,16 @@ struct rh_decode_call {
       }
       hp.mark("sync");
       check_bad(hctrl.ptr());
-      if (published && timed_size && !single) {      // the tile statistics rh_k_publish summed (include/ruhvro_hip.h RH_CTR_*_TILES)
+      const uint32_t lflag = *(const uint32_t*)(hctrl.ptr() + 8);
+      // a tile past the LDS window and no ranged pair in this call: nothing was emitted.  The refused attempt counts nothing
+      // (its tiles past the window never wrote their flag words, and the device summed none): the repeat of the call does.
+      if (lflag & rh::LF_NEED_RANGED) {
+        ctrl->b.clean = published;
+        s->ranged_calls.store(kRangedKeep, std::memory_order_relaxed);
+        r.arena.release();
+        throw NeedRanged();
+      }
+      if (published && timed_size && !single) {      // the tile statistics the scan launch summed (include/ruhvro_hip.h RH_CTR_*_TILES)
         const uint32_t* stw = (const uint32_t*)(hctrl.ptr() + 32);
         count(RH_CTR_TILES, nblocks);
         count(RH_CTR_CAREFUL_TILES, stw[0]); count(RH_CTR_OVER_WINDOW_TILES, stw[1]);
@@ -563,13 +574,6 @@ struct rh_decode_call {
         else { uint32_t v = s->ranged_calls.load(std::memory_order_relaxed); if (v) s->ranged_calls.compare_exchange_weak(v, v - 1, std::memory_order_relaxed); }
       }
       if (K > 0) std::memcpy(totals.data(), hctrl.ptr() + o_tot, 8ull * K * k);
-      const uint32_t lflag = *(const uint32_t*)(hctrl.ptr() + 8);
-      if (lflag & rh::LF_NEED_RANGED) {      // a tile past the LDS window and no ranged pair in this call: nothing was emitted
-        ctrl->b.clean = published;
-        s->ranged_calls.store(kRangedKeep, std::memory_order_relaxed);
-        r.arena.release();
-        throw NeedRanged();
-      }
       if (single) {
         ctrl->b.clean = published;
         if (lflag) {            // a column outgrew its capacity (or the capacity layout was refused): the two-pass path decides
@@ -602,7 +606,7 @@ struct rh_decode_call {
         r.arena_bytes = std::max<uint64_t>(*(const uint64_t*)(hctrl.ptr() + 16), kAlign);
       }
     } else {
-      count(RH_CTR_TWO_SYNC_CALLS);
+      count(RH_CTR_TWO_SYNC_CALLS);      // (this path counts no tile statistics: rh_k_scan sums none)
       if (timed_size) {
         HIPCHK(hipMemcpyAsync(hctrl.ptr(), ctrl->ptr(), ctrl_bytes, hipMemcpyDeviceToHost, stream));
         HIPCHK(hipStreamSynchronize(stream));

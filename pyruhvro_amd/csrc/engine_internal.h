@@ -52,7 +52,8 @@ int rh_launch_init(void* const* bufptr, const uint64_t* bufsize, const rh::BufDe
                    const unsigned long long* ctrl, void* stream);
 int rh_launch_layout(const rh::LParams* L, void* stream);
 int rh_launch_publish(void* ctrl, void* host, uint32_t head_words, uint32_t null_entries, uint32_t flag_word, uint32_t token, uint32_t nslots,
-                      const uint32_t* tileflag, uint32_t nflags, uint32_t stat_word, void* stream);
+                      void* stream);
+int rh_launch_tile_stats(void* ctrl, const uint32_t* tileflag, uint32_t nflags, void* stream);
 int rh_launch_emit(const rh::KParams* P, uint32_t lds_bytes, void* stream, void* start, void* stop);
 int rh_set_max_lds(uint32_t bytes);
 // the generic kernels of a projected schema (kernels.hip: the interpreter with the F_DROP dispatch of walk_drop.h)
@@ -376,7 +377,7 @@ struct rh_schema {
   // keeps changing character stays on the two-pass form, one outlier batch costs eight calls).
   std::vector<double> per_row;
   // Tiles past the LDS window: calls of this schema that still launch the ranged kernels behind the size / emit kernels -- set to
-  // kRangedKeep by every settled call that met such tiles (rh_k_publish's tile statistics), counted down by the others.
+  // kRangedKeep by every settled call that met such tiles (the call's tile statistics: control words 8..11, summed by the scan launch), counted down by the others.
   std::atomic<uint32_t> ranged_calls{0};
   uint32_t single_cooldown = 0, single_backoff = 0;      // calls the single pass sits out after a fail-over (8, 16, ... 1024; a success clears it)
 };

@@ -333,6 +333,52 @@ extern "C" __global__ void __launch_bounds__(kWideTile) rh_k_size_wp(KParams P) 
 extern "C" __global__ void __launch_bounds__(kBlock) rh_k_scan(KParams P);
 
 // --------------------------------------------------------------------------
+// The call's tile statistics: the size pass's per-tile flag words (program.h TileFlag) summed into words 8..11 of the
+// control block -- careful tiles, tiles past the window, re-walked wavefronts, sub-tiled tiles, in that order: what
+// rh_engine_counters reports.  The sums are taken where the work is already spread over workgroups (rh_k_scan_layout;
+// rh_k_tile_stats for a call that scans nothing), every load independent of the others; rh_k_publish carries the four
+// words to the host with the rest of the head and re-zeroes them.  ONE workgroup of rh_k_publish summed them at first:
+// 153 dependent trips to HBM per thread at 10M records, 38 us at the end of every call (profiles/r07_tilestats_ab.md).
+// --------------------------------------------------------------------------
+struct TileStat { uint32_t car = 0, over = 0, rew = 0, sub = 0; };
+__device__ __forceinline__ void tile_stat_add(TileStat& t, uint32_t f) {
+  t.car += (f >> 1) & 1u; t.over += (f >> 2) & 1u; t.sub += (f >> 3) & 1u; t.rew += (f >> 8) & 0xFFu;
+}
+// tiles [lo, hi) from this thread's third word on (the first two are the caller's, requested as early as it can), four loads in flight
+__device__ __forceinline__ void tile_stats_rest(TileStat& t, const uint32_t* tileflag, uint32_t lo, uint32_t hi) {
+  for (uint64_t i = (uint64_t)lo + threadIdx.x + 2 * kBlock; i < hi; i += 4 * kBlock) {
+    uint32_t f[4];
+#pragma unroll
+    for (uint32_t j = 0; j < 4; j++) f[j] = i + j * kBlock < hi ? tileflag[i + j * kBlock] : 0u;
+#pragma unroll
+    for (uint32_t j = 0; j < 4; j++) tile_stat_add(t, f[j]);
+  }
+}
+// Workgroup sums -> control words 8..11.  A sum that is zero is not added: a call whose tiles are all plain (the usual
+// one) issues no atomic.  `refused`: the size kernel refused the call (LF_NEED_RANGED: tiles past the window returned at
+// once and left their flag words UNWRITTEN, in pooled workspace) -- nothing is added, the repeat of the call counts.
+// All 256 threads call this; wstat = 16 LDS words.  The adds are thread 0's, so that its release fence orders them too.
+__device__ __forceinline__ void tile_stats_commit(uint32_t* ctrl32, const TileStat& t, bool refused, uint32_t* wstat) {
+  const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  uint32_t v[4] = {0, 0, 0, 0};
+  if (__any((t.car | t.over | t.rew | t.sub) != 0)) {      // (wave-uniform)
+    v[0] = wave_sum(t.car); v[1] = wave_sum(t.over); v[2] = wave_sum(t.rew); v[3] = wave_sum(t.sub);
+  }
+  if (lane == 0) {
+#pragma unroll
+    for (int j = 0; j < 4; j++) wstat[wave * 4 + j] = v[j];
+  }
+  __syncthreads();
+  if (threadIdx.x == 0 && !refused) {
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+      const uint32_t sum = wstat[j] + wstat[4 + j] + wstat[8 + j] + wstat[12 + j];
+      if (sum) __hip_atomic_fetch_add(ctrl32 + 8 + j, sum, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+  }
+}
+
+// --------------------------------------------------------------------------
 // k_scan + k_layout in ONE launch (the single-submission path): every workgroup scans its (counter, chunk) segment
 // like rh_k_scan; the workgroup that finishes LAST (ticket in control word [1] high half, zeroed with the control
 // words) lays the arena out from the chunk totals all of them left.  One launch and one inter-kernel gap less per
@@ -468,7 +514,30 @@ extern "C" __global__ void __launch_bounds__(kBlock) rh_k_scan_layout(KParams P,
   __shared__ uint32_t wt[4];
   __shared__ uint32_t flags;
   __shared__ uint32_t last;
+  __shared__ uint32_t wstat[16];
+  // The tile statistics ride along (tile_stats_commit above): workgroup (counter kk, chunk ch) takes the kk-th of K slices of
+  // its chunk's tiles [b0, b1), so every tile of the call is counted exactly once.  The first two words per thread -- all
+  // there is of a slice at 10M records / 8 chunks (407 words) -- and the layout flag are requested HERE, ahead of the
+  // scan's first barrier: their latency passes behind the blocksum loads.  (The flag word is final: the last workgroup
+  // writes it only after every workgroup's ticket, and this read is before ours.)
+  uint32_t* const ctrl32 = reinterpret_cast<uint32_t*>(L.ctrl);
+  uint32_t s_lo, s_hi;
+  {
+    const uint32_t kk = blockIdx.x % (uint32_t)P.K, ch = blockIdx.x / (uint32_t)P.K;
+    const uint32_t b0 = ch * P.bpc, b1 = ch == P.k - 1 ? P.nblocks : (ch + 1) * P.bpc;
+    s_lo = b0 + (uint32_t)((uint64_t)(b1 - b0) * kk / (uint32_t)P.K);
+    s_hi = b0 + (uint32_t)((uint64_t)(b1 - b0) * (kk + 1) / (uint32_t)P.K);
+  }
+  const uint32_t i0 = s_lo + threadIdx.x;
+  const uint32_t f0 = i0 < s_hi ? P.tileflag[i0] : 0u;
+  const uint32_t f1 = i0 + kBlock < s_hi ? P.tileflag[i0 + kBlock] : 0u;
+  const bool refused = (ctrl32[2] & (uint32_t)LF_NEED_RANGED) != 0;
   scan_segment(P, wt);
+  TileStat ts;
+  tile_stat_add(ts, f0);
+  tile_stat_add(ts, f1);
+  tile_stats_rest(ts, P.tileflag, s_lo, s_hi);
+  tile_stats_commit(ctrl32, ts, refused, wstat);                // (thread 0's adds: ahead of its fence and ticket)
   if (threadIdx.x == 0) {
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");          // this workgroup's total before its ticket
     uint32_t* ticket = reinterpret_cast<uint32_t*>(L.ctrl) + 3;
@@ -479,6 +548,25 @@ extern "C" __global__ void __launch_bounds__(kBlock) rh_k_scan_layout(KParams P,
   __syncthreads();
   if (!last) return;
   layout_body(L, run_sum, &flags);
+}
+
+// --------------------------------------------------------------------------
+// k_tile_stats: the tile statistics of a call that has a size pass and nothing to scan (K == 0: a projection that dropped
+// every variable-length column but must still walk them, schema.h size_always) -- rh_k_layout runs alone there.  Workgroup
+// b of gridDim.x takes the b-th slice of the flag words.  Launched between the size pass and rh_k_layout.
+// (The two-submission path -- RUHVRO_HIP_TWO_SYNC, a schema's first call -- publishes no statistics, as before:
+//  rh_k_scan sums nothing and this kernel is not launched there.)
+// --------------------------------------------------------------------------
+extern "C" __global__ void __launch_bounds__(kBlock) rh_k_tile_stats(uint32_t* ctrl32, const uint32_t* tileflag, uint32_t nflags) {
+  __shared__ uint32_t wstat[16];
+  const uint32_t lo = (uint32_t)((uint64_t)nflags * blockIdx.x / gridDim.x);
+  const uint32_t hi = (uint32_t)((uint64_t)nflags * (blockIdx.x + 1) / gridDim.x);
+  const uint32_t i0 = lo + threadIdx.x;
+  TileStat ts;
+  tile_stat_add(ts, i0 < hi ? tileflag[i0] : 0u);
+  tile_stat_add(ts, i0 + kBlock < hi ? tileflag[i0 + kBlock] : 0u);
+  tile_stats_rest(ts, tileflag, lo, hi);
+  tile_stats_commit(ctrl32, ts, (ctrl32[2] & (uint32_t)LF_NEED_RANGED) != 0, wstat);
 }
 
 // --------------------------------------------------------------------------
@@ -493,28 +581,14 @@ extern "C" __global__ void __launch_bounds__(kBlock) rh_k_scan_layout(KParams P,
 // barrier): the host spins on that word in its pinned block instead of waiting for a stream event -- an event record
 // between two calls cost the GPU 5.7 us of idle time per call (profiles/r03aj_timeline.txt), and the spin sees the
 // token ~3 us sooner than hipStreamSynchronize returns (tools/synclat.hip).
-// ABI 7: the size pass's per-tile flags (program.h TileFlag) are summed here into four words of the head -- what
-// rh_engine_counters reports as careful / over-window / sub-tiled tiles and re-walked wavefronts (nflags = 0: no size pass ran).
+// ABI 7: words 8..11 of the head are the call's tile statistics (tile_stats_commit above; zero when no size pass ran).  They
+// are summed by the scan launch and leave with the head copy below: this kernel's duration does not depend on the number
+// of tiles (6.3 us at 10M records, 6.0 us at 1M; 44.5 us at 10M while the sums were taken here: profiles/r07_tilestats_ab.md).
 extern "C" __global__ void __launch_bounds__(kBlock) rh_k_publish(uint32_t* ctrl, uint32_t* host, uint32_t head_words,
-                                                                 uint32_t null_entries, uint32_t flag_word, uint32_t token, uint32_t nslots,
-                                                                 const uint32_t* tileflag, uint32_t nflags, uint32_t stat_word) {
-  __shared__ uint32_t stat[4];
-  if (threadIdx.x < 4) stat[threadIdx.x] = 0;
-  __syncthreads();
-  for (uint32_t i = threadIdx.x; i < head_words; i += kBlock) {      // control words + chunk totals, as they are
+                                                                 uint32_t null_entries, uint32_t flag_word, uint32_t token, uint32_t nslots) {
+  for (uint32_t i = threadIdx.x; i < head_words; i += kBlock) {      // control words, tile statistics + chunk totals, as they are
     host[i] = ctrl[i];
     ctrl[i] = 0;
-  }
-  if (nflags) {
-    uint32_t car = 0, over = 0, sub = 0, rew = 0;
-    for (uint32_t i = threadIdx.x; i < nflags; i += kBlock) {
-      const uint32_t f = tileflag[i];
-      car += (f >> 1) & 1u; over += (f >> 2) & 1u; sub += (f >> 3) & 1u; rew += (f >> 8) & 0xFFu;
-    }
-    car = wave_sum(car); over = wave_sum(over); sub = wave_sum(sub); rew = wave_sum(rew);
-    if ((threadIdx.x & 63) == 0) { atomicAdd(&stat[0], car); atomicAdd(&stat[1], over); atomicAdd(&stat[2], rew); atomicAdd(&stat[3], sub); }
-    __syncthreads();
-    if (threadIdx.x < 4) host[stat_word + threadIdx.x] = stat[threadIdx.x];
   }
   uint32_t* slots = ctrl + head_words;                               // [null_entries][nslots] (program.h null_slots_for)
   for (uint32_t e = threadIdx.x; e < null_entries; e += kBlock) {
@@ -672,10 +746,17 @@ extern "C" int rh_launch_init(void* const* bufptr, const uint64_t* bufsize, cons
   return (int)hipGetLastError();
 }
 extern "C" int rh_launch_publish(void* ctrl, void* host, uint32_t head_words, uint32_t null_entries, uint32_t flag_word, uint32_t token,
-                                 uint32_t nslots, const uint32_t* tileflag, uint32_t nflags, uint32_t stat_word, void* stream) {
+                                 uint32_t nslots, void* stream) {
   (void)hipGetLastError();      // (an earlier, unrelated error -- a hipStreamQuery that said "not ready" -- must not be read as this launch\'s)
   hipLaunchKernelGGL(rh::rh_k_publish, dim3(1), dim3(rh::kBlock), 0, (hipStream_t)stream, (uint32_t*)ctrl, (uint32_t*)host, head_words,
-                     null_entries, flag_word, token, nslots, tileflag, nflags, stat_word);
+                     null_entries, flag_word, token, nslots);
+  return (int)hipGetLastError();
+}
+// (a call with a size pass and no scan launch: one workgroup per 512 flag words -- two loads per thread --, 64 at the most)
+extern "C" int rh_launch_tile_stats(void* ctrl, const uint32_t* tileflag, uint32_t nflags, void* stream) {
+  (void)hipGetLastError();
+  const uint32_t wgs = nflags / 512 < 1 ? 1u : nflags / 512 > 64 ? 64u : nflags / 512;
+  hipLaunchKernelGGL(rh::rh_k_tile_stats, dim3(wgs), dim3(rh::kBlock), 0, (hipStream_t)stream, (uint32_t*)ctrl, tileflag, nflags);
   return (int)hipGetLastError();
 }
 extern "C" int rh_launch_layout(const rh::LParams* L, void* stream) {
