@@ -277,7 +277,9 @@ enum {
   RH_CTR_BACKGROUND_COMPILES = 8, /* kernel compile jobs started behind a call that went ahead on the generic kernels (ABI 6) */
   /* ABI 7: what the walks met, summed over the tiles of every single-submission call on the device (the scan launch sums the
    * size pass's per-tile flags, the call's last kernel hands the sums over; a call's first run on a schema, a call repeated with an
-   * exact arena and an attempt refused for want of the ranged kernels are not counted).  A tile
+   * exact arena and an attempt refused for want of the ranged kernels are not counted).  A call without a size pass (a schema
+   * without variable-length output) counts only its tiles past the window -- over_window_tiles, subtiled_tiles -- in its emit
+   * kernels, on every path.  A tile
    * is one workgroup's records (256, or 64 for wide schemas); all of these are 0 on input that stays inside the fast wire forms. */
   RH_CTR_TILES = 9,             /* tiles of the calls counted below                                                           */
   RH_CTR_CAREFUL_TILES = 10,    /* tiles the emit pass walked with the careful form (an anomaly in the size pass, or no window)  */

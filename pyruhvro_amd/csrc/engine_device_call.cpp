@@ -104,6 +104,17 @@ struct rh_decode_call {
     throw DecodeError(format_error(ei));
   }
 
+  // A call without a size pass (a schema without counters): its emit kernels counted the tiles past the window they walked
+  // (control words 9 and 11: spec_flat.h, kernels.hip k_emit_body) -- the only tile statistics of such a call, and what tells the schema's
+  // next calls to launch the ranged pair.  hctrl holds the head of the control block as the call's last emit pass left it.
+  void learn_unsized_tiles() {
+    if (timed_size || single || n == 0) return;
+    const uint32_t* stw = (const uint32_t*)(hctrl.ptr() + 32);
+    count(RH_CTR_OVER_WINDOW_TILES, stw[1]); count(RH_CTR_SUBTILED_TILES, stw[3]);
+    if (stw[1]) s->ranged_calls.store(kRangedKeep, std::memory_order_relaxed);
+    else { uint32_t v = s->ranged_calls.load(std::memory_order_relaxed); if (v) s->ranged_calls.compare_exchange_weak(v, v - 1, std::memory_order_relaxed); }
+  }
+
   // host statement of the layout (same rule, same table order as rh_k_layout): fills the result's tables
   void layout_host() {
     r.data_bytes = totals;
@@ -307,8 +318,10 @@ struct rh_decode_call {
     }
     // The ranged pair behind the size / emit kernels (spec_body.h ranged_tile): while the schema's recent calls met tiles past the
     // LDS window (rh_schema::ranged_calls, fed by the call's tile statistics), or when the caller insists on the specialised
-    // kernels.  A call that meets such tiles without it takes the fallback (the careful walk from global memory) and, large enough,
-    // starts the pair's compile in the background.  RUHVRO_HIP_RANGED=0 / 1: never / always (A/B, tests).
+    // kernels.  A call that meets such tiles without it is refused by its size kernel (LF_NEED_RANGED) and repeated on the generic
+    // kernels (NeedRanged); a schema without counters has no size pass, so its emit kernel walks such tiles itself, carefully and
+    // from global memory, and counts them (spec_flat.h; learn_unsized_tiles).  Either way the schema's next calls launch the pair, compiled
+    // in the background if need be.  RUHVRO_HIP_RANGED=0 / 1: never / always (A/B, tests).
     if (sk) {
       const long force = env_long("RUHVRO_HIP_RANGED", -1, 0, 1);
       const bool want = force == 1 || (force != 0 && (s->ranged_calls.load(std::memory_order_relaxed) > 0 || mode == RH_KERNEL_SPECIALIZED));
@@ -476,15 +489,16 @@ struct rh_decode_call {
         ev.rec(2, stream);
       } else if (!fused && rh_launch_scan(&P, stream, ev.at(5), ev.at(2))) throw HipError("k_scan launch failed");
     } else {
-      // no size pass (no variable-length output): nobody classified the tiles, so the emit kernel walks all of them carefully
-      P.all_careful = 1;
+      // no size pass (no variable-length output): nobody classified the tiles, so the emit kernel walks all of them carefully --
+      // those past the window too, which it counts (kAcNoSizePass: spec_flat.h, kernels.hip k_emit_body)
+      P.all_careful = 1u | kAcNoSizePass;
       if (sized) HIPCHK(hipEventRecord(sized, stream));
     }
     // RUHVRO_HIP_NO_TRUST=1 (debugging aid): the emit pass walks EVERY tile with its own bounds and anomaly checks instead of
     // trusting the size pass's verdict on the same bytes (walk.h RH_TRUST) -- what a caller that suspects its input buffers
     // change between the two passes of an RH_ASYNC call turns on; the GPU suite passes with it (tests/test_async_device.py)
     static const bool no_trust = env_long("RUHVRO_HIP_NO_TRUST", 0, 0, 1) != 0;
-    if (no_trust) P.all_careful = 1;
+    if (no_trust) P.all_careful |= 1u;
     hp.mark("size+scan_launch");
     basis = (double)payload + 64.0 * (double)n;
     if (fused) {
@@ -554,16 +568,18 @@ struct rh_decode_call {
         HIPCHK(hipStreamSynchronize(stream));
       }
       hp.mark("sync");
-      check_bad(hctrl.ptr());
       const uint32_t lflag = *(const uint32_t*)(hctrl.ptr() + 8);
       // a tile past the LDS window and no ranged pair in this call: nothing was emitted.  The refused attempt counts nothing
       // (its tiles past the window never wrote their flag words, and the device summed none): the repeat of the call does.
+      // Ahead of the error check: a refused tile was not walked, so first_bad is the lowest malformed record of the OTHER tiles
+      // only -- the repeat walks every tile and reports the lowest of all.
       if (lflag & rh::LF_NEED_RANGED) {
         ctrl->b.clean = published;
         s->ranged_calls.store(kRangedKeep, std::memory_order_relaxed);
         r.arena.release();
         throw NeedRanged();
       }
+      check_bad(hctrl.ptr());
       if (published && timed_size && !single) {      // the tile statistics the scan launch summed (include/ruhvro_hip.h RH_CTR_*_TILES)
         const uint32_t* stw = (const uint32_t*)(hctrl.ptr() + 32);
         count(RH_CTR_TILES, nblocks);
@@ -610,16 +626,17 @@ struct rh_decode_call {
       if (timed_size) {
         HIPCHK(hipMemcpyAsync(hctrl.ptr(), ctrl->ptr(), ctrl_bytes, hipMemcpyDeviceToHost, stream));
         HIPCHK(hipStreamSynchronize(stream));
-        check_bad(hctrl.ptr());
-        if (*(const uint32_t*)(hctrl.ptr() + 8) & rh::LF_NEED_RANGED) {
+        if (*(const uint32_t*)(hctrl.ptr() + 8) & rh::LF_NEED_RANGED) {      // (ahead of the error check, as above)
           ctrl->b.clean = false;
           s->ranged_calls.store(kRangedKeep, std::memory_order_relaxed);
           throw NeedRanged();
         }
+        check_bad(hctrl.ptr());
         std::memcpy(totals.data(), hctrl.ptr() + o_tot, 8ull * K * k);
       }
       exact_tail();
     }
+    learn_unsized_tiles();
     if (n > 0 && basis > 0 && !single) {
       const double slots = (double)n_entries * (double)kAlign;
       s->arena_ratio.store(std::max(0.0, (double)r.arena_bytes - slots) / basis + 1e-9);
@@ -879,6 +896,12 @@ void settle(rh_device_result* r) {
     } catch (const NeedWideIndex&) {
       if (generic) throw;
       count(RH_CTR_WIDE_FALLBACKS);
+      o.flags = (o.flags & ~3) | RH_KERNEL_GENERIC;
+      r2.reset(decode_device_impl1(call->s, call->d_data, call->d_offsets, call->data_len, call->n, call->num_chunks, &o,
+                                   call->want_stats ? &st2 : nullptr, call->geo));
+    } catch (const NeedRanged&) {      // (the two-pass repeat of a single-pass call, launched without the ranged pair, met a tile past the window)
+      if (generic) throw;
+      count(RH_CTR_RANGED_RETRIES);
       o.flags = (o.flags & ~3) | RH_KERNEL_GENERIC;
       r2.reset(decode_device_impl1(call->s, call->d_data, call->d_offsets, call->data_len, call->n, call->num_chunks, &o,
                                    call->want_stats ? &st2 : nullptr, call->geo));

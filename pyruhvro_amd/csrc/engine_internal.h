@@ -85,6 +85,9 @@ struct NeedRanged {};      // a tile past the LDS window met specialised kernels
 struct NeedTwoPass {};     // the single-pass form outgrew a column capacity (or needs what only the two-pass layout checks): repeat
 
 extern std::atomic<uint64_t> g_counters[RH_CTR_COUNT];     // rh_engine_counters (include/ruhvro_hip.h)
+// KParams::all_careful, bit 1 (bit 0: every tile carefully): the call has no size pass, so its emit kernels count the tiles past the
+// LDS window themselves (the generic emit kernel tests this bit; the specialised kernels of such a schema are generated for it)
+constexpr uint32_t kAcNoSizePass = 2;
 constexpr uint32_t kRangedKeep = 64;      // calls a schema keeps launching its ranged kernels after the last tile past the LDS window
 inline void count(int which, uint64_t by = 1) { g_counters[which].fetch_add(by, std::memory_order_relaxed); }
 

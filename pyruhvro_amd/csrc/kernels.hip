@@ -651,6 +651,9 @@ __device__ __forceinline__ void k_emit_body(const KParams& P) {
   const uint64_t wb16 = wb & ~15ull;
   const bool fits = (we - wb16) <= (uint64_t)P.win_bytes;
   if (fits) stage_window<T>(P, s.win, wb16, we, tid);
+  // (bit 1 of all_careful, engine_internal.h kAcNoSizePass: the call has no size pass -- K == 0 -- so nobody counted the tiles past
+  //  the window: control word 9 of the tile statistics, as the specialised emit kernels of such a schema do, spec_flat.h)
+  else if ((P.all_careful & 2u) != 0 && tid == 0) atomicAdd(reinterpret_cast<uint32_t*>(P.first_bad) + 9, 1u);
   for (int k = 0; k < P.KL; k++) s.cnt[k * T + tid] = 0;
   for (int i = tid; i < P.nnodes; i += T) s.nullcnt[i] = 0;
   for (int i = tid; i < P.nbuf; i += T)

@@ -43,6 +43,8 @@ def known_schemas() -> List[str]:
             out.append(c[1])
         for c in cases.error_cases():
             out.append(c[1])
+        # tiles past the smallest LDS window (tests/test_form_switch.py; a case table without them has nothing to add)
+        out += cases.form_switch_schemas() if hasattr(cases, "form_switch_schemas") else []
         for c in cases.differential_cases():
             out.append(c[1])
         out.append(cases.logical_case()[0])
@@ -78,7 +80,11 @@ def single_pass_schemas() -> List[str]:
     """The schemas whose single-pass kernel (rh_spec_fused) a bench line or a test runs: the only ones build() compiles it for --
     it is the most expensive of a schema's five kernels and opt-in; every other schema gets it on first request."""
     from avrogen.schemas import SCHEMAS
-    return [SCHEMAS[k] for k in ("full", "cfg3", "flat4", "array_and_map", "nullable_primitives", "t_enum", "t_union")]
+    import cases
+    out = [SCHEMAS[k] for k in ("full", "cfg3", "flat4", "array_and_map", "nullable_primitives", "t_enum", "t_union")]
+    if hasattr(cases, "form_switch_schemas"):      # (tests/test_form_switch.py: single pass -> two pass -> generic)
+        out += [cases.form_switch_schema("id_str", "_single"), cases.form_switch_full_skewed_schema()]
+    return out
 
 
 if __name__ == "__main__":

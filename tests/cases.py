@@ -9,10 +9,13 @@ and the GPU parity tests.
   error_cases()         malformed datums + the exact message the reference raises
                         (fast_decode.rs:575,591,646,849,866,874,884,898,906,910);
   nesting_cases()       schemas the reference never tests (union-of-record, list of
-                        lists, nullable containers, children domains with bitmaps).
+                        lists, nullable containers, children domains with bitmaps);
+  form_switch_cases()   small-record inputs with a run of large records: tiles past the
+                        smallest LDS window (8 KiB) without any test hook.
 """
 from __future__ import annotations
 
+import functools
 import json
 import struct
 from typing import List, Tuple
@@ -591,4 +594,89 @@ def deep_nesting_cases():
         return {"u": un(level - 1, r + 1), "k": r * 1_000_003 + level}
     vals = [{"u": un(10, r)} for r in range(160)]
     out.append(("unions_10_deep", s, _enc(s, vals)))
+    return out
+
+
+# ---- tiles past the LDS window of a small-record call (tests/test_form_switch.py) ---------------------------------------------------
+FORM_SWITCH_KINDS = ("longs8", "longs8_nullable", "id_str")
+# One schema object -- kernels loaded, size history, ranged-pair history -- per tag: a test that depends on a schema's history
+# decodes a schema no other test has touched.  The record's name is the only difference between them.
+FORM_SWITCH_TAGS = (("",) + tuple(f"_{mode}{k}{road}" for mode in "ags" for k in (1, 3, 7, "_hook") for road in ("", "a", "h")) +
+                    ("_flat", "_first", "_later", "_single", "_split", "_history"))
+BIG_RUN = {"longs8": (5000, 5768), "longs8_nullable": (5000, 5768), "id_str": (0, 768)}      # the records of 10-byte varints / 100-character strings
+
+
+def form_switch_schema(kind: str, tag: str = "") -> str:
+    assert kind in FORM_SWITCH_KINDS and tag in FORM_SWITCH_TAGS, (kind, tag)
+    if kind == "id_str":
+        fields = [{"name": "id", "type": "long"}, {"name": "s", "type": "string"}]
+    else:
+        t = "long" if kind == "longs8" else ["null", "long"]
+        fields = [{"name": f"c{i}", "type": t} for i in range(8)]
+    return json.dumps({"type": "record", "name": f"FormSwitch_{kind}{tag}", "fields": fields})
+
+
+def form_switch_full_skewed_schema() -> str:
+    """The schema of avrogen's full_skewed records under a name of its own: the size and capacity history of SCHEMAS["full"] is
+    shared by many tests."""
+    return json.dumps(dict(json.loads(SCHEMAS["full_skewed"]), name="FormSwitch_full_skewed"))
+
+
+def form_switch_schemas() -> List[str]:
+    """Every schema tests/test_form_switch.py decodes (scripts/known_schemas.py compiles their kernels ahead of a GPU run)."""
+    return [form_switch_schema(kind, tag) for kind in FORM_SWITCH_KINDS for tag in FORM_SWITCH_TAGS] + [form_switch_full_skewed_schema()]
+
+
+@functools.lru_cache(maxsize=None)
+def _form_switch_records(kind: str) -> Tuple[bytes, ...]:
+    def mix(r, i):      # a fixed 64-bit scramble of (record, column)
+        x = (r * 0x9E3779B97F4A7C15 + i * 0xBF58476D1CE4E5B9 + 0x94D049BB133111EB) & ((1 << 64) - 1)
+        x ^= x >> 31
+        return (x * 0xD6E8FEB86659FD93) & ((1 << 64) - 1)
+    out = []
+    if kind == "id_str":
+        for r in range(6000):
+            text = (f"{r:04d}-" + "abcdefghij" * 10)[:100] if r < 768 else "abcdefghijklmnopqrstuvwxyz"[r % 26]
+            out.append(zigzag(r) + zigzag(len(text)) + text.encode())
+        return tuple(out)
+    lo, hi = BIG_RUN[kind]
+    for r in range(20_000):
+        b = bytearray()
+        for i in range(8):
+            h = mix(r, i)
+            if lo <= r < hi:      # |v| > 2^62, both signs: ten bytes each (2^62 itself zigzags to 2^63, -2^62 to 2^63 - 1: nine bytes)
+                v = (1 << 62) + 1 + (h >> 3) % ((1 << 62) - 2)
+                v = -v if h & 1 else v
+            else:                 # one byte each
+                v = (h >> 8) % 128 - 64
+            if kind == "longs8_nullable":
+                if h % 10 == 7:
+                    b += zigzag(0)               # the null branch
+                    continue
+                b += zigzag(1)
+            b += zigzag(v)
+        out.append(bytes(b))
+    return tuple(out)
+
+
+def form_switch_cases(tag: str = ""):
+    """Inputs whose mean record is small enough for the smallest LDS window (8,192 bytes: max(8192, mean * 256 * 1.15 + 2048)) and
+    that hold a run of 768 large records -- at least two whole 256-record tiles of 20 KB and more wherever the chunks start -- so
+    that a call meets tiles past the window with no test hook.  longs8 / longs8_nullable have no variable-length output (no
+    counter, no size pass); id_str has.  The *_damaged* lists are the sound ones with two malformed records each: the lower one
+    sits inside a tile past the window, the higher one inside a tile that fits.
+    -> list of (name, schema_json, records)."""
+    out = [(kind, form_switch_schema(kind, tag), list(_form_switch_records(kind))) for kind in FORM_SWITCH_KINDS]
+    recs = list(_form_switch_records("id_str"))
+    recs[100] = recs[100][:50]                                # cut inside its string body
+    recs[3000] = zigzag(3000) + zigzag(-1)                     # a negative string length
+    out.append(("id_str_damaged", form_switch_schema("id_str", tag), recs))
+    recs = list(_form_switch_records("longs8"))
+    recs[5300] = recs[5300][:35]                              # cut in the middle of the fourth column's varint
+    recs[9000] = recs[9000][:5]                               # cut behind the fifth column
+    out.append(("longs8_damaged", form_switch_schema("longs8", tag), recs))
+    # (a long column knows two messages, and both cuts above raise the same one: this list can tell the two records apart)
+    recs = list(recs)
+    recs[9000] = recs[9000][:4] + b"\x80" * 10 + b"\x00" + recs[9000][5:]      # the fifth column: a varint of eleven bytes
+    out.append(("longs8_damaged_apart", form_switch_schema("longs8", tag), recs))
     return out
