@@ -287,9 +287,61 @@ enum {
   RH_CTR_REWALKED_WAVES = 12,   /* wavefronts the size pass walked twice (a record outside the fast wire forms, or malformed)  */
   RH_CTR_SUBTILED_TILES = 13,   /* over-window tiles that were staged through the window in record ranges (not walked from HBM) */
   RH_CTR_RANGED_RETRIES = 14,   /* calls repeated on the generic kernels: a tile past the window met specialised kernels whose ranged pair was not loaded yet */
-  RH_CTR_COUNT = 15
+  /* Tolerant decode (rh_decode*_tolerant below; appended without a change of RH_ABI_VERSION) */
+  RH_CTR_TOLERANT_CALLS = 15,   /* tolerant decode calls                                                                      */
+  RH_CTR_TOLERANT_REPAIRS = 16, /* ... of which met a malformed record: they ran the validation kernel and a second decode    */
+  RH_CTR_COUNT = 17
 };
 uint32_t rh_engine_counters(uint64_t* out, uint32_t n);
+
+/* Tolerant decode.  A strict decode call (rh_decode / rh_decode_packed / rh_decode_device) is aborted by its lowest malformed
+ * record, as the reference's is.  A tolerant call returns the batches of the strict call -- same number of chunks, same chunk
+ * boundaries, same rows -- in which every malformed record has been REPLACED by the schema's placeholder datum, and the list of
+ * ALL malformed records as (index, message), ascending by index; `message` is exactly what the strict call raises when that
+ * record is the lowest failing one.  In other words: the batches are, buffer for buffer, those of the strict call on the input
+ * with the placeholder in place of every listed record.
+ * The placeholder is the shortest datum of the schema the strict decoder accepts (null wherever the schema allows null, zero /
+ * empty elsewhere): null -> nothing; boolean, int, long and their logical types, enum, string, bytes, array, map -> 00; float /
+ * double -> 4 / 8 zero bytes; uuid on string -> the 36-character nil uuid behind its length; decimal on bytes -> 02 00;
+ * fixed(n) and decimal / duration / uuid over it -> n zero bytes; record -> its fields' placeholders; a union with a null branch
+ * -> the index of its first null branch; any other union -> branch 0 and that branch's placeholder.
+ * The call is optimistic: it IS the strict call, and a clean input costs exactly what the strict call costs (no extra launch,
+ * allocation or copy).  Only when the strict call fails on a record, a validation kernel walks all n records, the malformed
+ * ones are replaced and the strict call runs again on the patched input (the device form gathers it into a new device buffer
+ * that the result owns).  More than `max_errors` malformed records (1024 is a sensible bound: beyond it the schema is wrong,
+ * not the data) fail the call with the strict call's error; max_errors = 0 is the strict call.  Errors that belong to no single
+ * record (offset overflow, runtime failures) are returned as by the strict call.  Projected schemas compose: the errors are the
+ * full decode's, the placeholder the full schema's.  RH_ASYNC is refused with RH_ERR_ARGUMENT; every other flag and field of
+ * rh_opts means what it means for the strict call.
+ * Added WITHOUT a change of RH_ABI_VERSION (7): a caller discovers these entry points by the presence of the symbols (dlsym). */
+/* The placeholder datum: *bytes (owned by the schema, valid until rh_schema_free) and *len. */
+int rh_schema_placeholder(const rh_schema* s, const uint8_t** bytes, uint64_t* len);
+/* The list of malformed records a call reports: opaque, released with rh_record_errors_free.  rh_record_errors_get: entry i
+ * (ascending record index) -> its record index, its error code and its message (owned by the list); any out pointer may be NULL. */
+typedef struct rh_record_errors rh_record_errors;
+uint64_t rh_record_errors_count(const rh_record_errors* e);
+int rh_record_errors_get(const rh_record_errors* e, uint64_t i, uint64_t* index, int* code, const char** message);
+void rh_record_errors_free(rh_record_errors* e);
+/* Validation alone: *out lists ALL malformed records of the input -- when there are more than max_errors, the max_errors
+ * lowest -- and *total_bad is their exact number.  Host input is uploaded in groups and validated on rh_opts.device (the first
+ * entry of rh_opts.devices for a multi-device option block). */
+int rh_validate(const rh_schema* s, const uint8_t* const* ptrs, const uint64_t* lens, uint64_t n, const rh_opts* opts,
+                uint64_t max_errors, rh_record_errors** out, uint64_t* total_bad, char** err);
+int rh_validate_packed(const rh_schema* s, const uint8_t* data, const uint64_t* offsets, uint64_t n, const rh_opts* opts,
+                       uint64_t max_errors, rh_record_errors** out, uint64_t* total_bad, char** err);
+int rh_validate_device(const rh_schema* s, const void* d_data, const void* d_offsets, uint64_t data_len, uint64_t n,
+                       const rh_opts* opts, uint64_t max_errors, rh_record_errors** out, uint64_t* total_bad, char** err);
+/* The tolerant forms of rh_decode, rh_decode_packed and rh_decode_device: their arguments, then max_errors and the list
+ * (*errors: empty for a clean input, NULL when the call fails). */
+int rh_decode_tolerant(const rh_schema* s, const uint8_t* const* ptrs, const uint64_t* lens, uint64_t n, uint64_t num_chunks,
+                       const rh_opts* opts, struct ArrowArray* out_chunks, uint32_t* out_k, rh_stats* stats, char** err,
+                       uint64_t max_errors, rh_record_errors** errors);
+int rh_decode_packed_tolerant(const rh_schema* s, const uint8_t* data, const uint64_t* offsets, uint64_t n, uint64_t num_chunks,
+                              const rh_opts* opts, struct ArrowArray* out_chunks, uint32_t* out_k, rh_stats* stats, char** err,
+                              uint64_t max_errors, rh_record_errors** errors);
+int rh_decode_device_tolerant(const rh_schema* s, const void* d_data, const void* d_offsets, uint64_t data_len, uint64_t n,
+                              uint64_t num_chunks, const rh_opts* opts, rh_device_result** out, rh_stats* stats, char** err,
+                              uint64_t max_errors, rh_record_errors** errors);
 
 /* Measurement hook, not part of the drop-in surface: the host-side gather of a `shards`-GPU rh_decode call (every shard's
  * record slices copied into its staging buffer by its own host thread + `threads_per_shard` helpers, all shards at once)

@@ -1,11 +1,19 @@
 """Drop-in module name: ``import pyruhvro`` resolves to the MI355X-native engine.
 
 Same five functions as the reference's PyO3 module (src/lib.rs:150-158); the three decode functions also take the
-keyword-only extension ``columns=[...]`` (decode only those top-level fields)."""
+keyword-only extension ``columns=[...]`` (decode only those top-level fields).  Beside them the tolerant decode: the
+``*_tolerant`` functions replace malformed records by ``placeholder_datum(schema)`` and report all of them."""
 from pyruhvro_amd import (  # noqa: F401
+    deserialize_array_tolerant,
+    deserialize_array_threaded_tolerant,
+    deserialize_binary_array_tolerant,
+    deserialize_to_device,
+    placeholder_datum,
+    validate_records,
     deserialize_array,
     deserialize_array_threaded,
     deserialize_array_threaded_spawn,
     serialize_record_batch,
     serialize_record_batch_spawn,
 )
+from pyruhvro_amd.cabi import RecordError  # noqa: F401,E402

@@ -231,6 +231,76 @@ def deserialize_binary_array(array, schema, num_chunks, *, columns=None):
     return cabi.decode_packed(data, offsets, schema, num_chunks, kernel=_kernel_mode, devices=_current_devices(), columns=columns)
 
 
+def _check_chunks(num_chunks):
+    if not isinstance(num_chunks, int) or isinstance(num_chunks, bool):
+        raise TypeError("argument 'num_chunks': expected int")
+    if num_chunks < 0:
+        raise OverflowError("can't convert negative int to unsigned")
+
+
+def _pack_records(records):
+    """list[bytes] or a pyarrow (Large)BinaryArray -> (payload, offsets) with at least one addressable payload byte."""
+    import numpy as np
+    from .device import _pack
+    if isinstance(records, (list, tuple)):
+        for r in records:
+            if not isinstance(r, (bytes, bytearray, memoryview)):
+                raise TypeError("argument 'list': expected a list of bytes")
+    data, offs = _pack(records)
+    return (data if len(data) else np.zeros(1, dtype=np.uint8)), offs
+
+
+def placeholder_datum(schema) -> bytes:
+    """Extension.  The datum a tolerant decode puts in the place of a malformed record: the shortest datum of the schema that the
+    strict decoder accepts -- null wherever the schema allows null, zero / empty elsewhere ("Tolerant decode")."""
+    from . import cabi
+    _get_schema(schema)
+    return cabi.placeholder_datum(schema)
+
+
+def validate_records(list, schema, *, max_errors=1024):  # noqa: A002
+    """Extension.  ALL malformed records of the list as ``[RecordError(index, message)]``, ascending by index (the ``max_errors``
+    lowest when there are more): ``message`` is what ``deserialize_array`` raises when that record is the first malformed one."""
+    from . import cabi
+    from .device import check_max_errors
+    _get_schema(schema)
+    data, offs = _pack_records(list)
+    return cabi.validate_packed(data, offs, schema, check_max_errors(max_errors), devices=_current_devices())
+
+
+def _decode_tolerant(records, schema, num_chunks, columns, max_errors):
+    from . import cabi
+    from .device import check_max_errors
+    _check_chunks(num_chunks)
+    _get_schema(schema, columns)
+    data, offs = _pack_records(records)
+    return cabi.decode_packed_tolerant(data, offs, schema, num_chunks, kernel=_kernel_mode, devices=_current_devices(),
+                                       columns=columns, max_errors=check_max_errors(max_errors))
+
+
+def deserialize_array_tolerant(list, schema, *, columns=None, max_errors=1024):  # noqa: A002
+    """Extension.  ``deserialize_array`` that a malformed record does not abort: returns ``(batch, errors)`` where the batch has
+    ``placeholder_datum(schema)`` decoded in the place of every malformed record (same row count) and ``errors`` lists all of
+    them as ``RecordError(index, message)``.  More than ``max_errors`` malformed records raise what ``deserialize_array``
+    raises.  Clean input costs what the strict call costs."""
+    batches, errors = _decode_tolerant(list, schema, 1, columns, max_errors)
+    return batches[0], errors
+
+
+def deserialize_array_threaded_tolerant(list, schema, num_chunks, *, columns=None, max_errors=1024):  # noqa: A002
+    """Extension.  ``deserialize_array_threaded`` in the tolerant form: ``(list[RecordBatch], errors)``, the chunking unchanged."""
+    return _decode_tolerant(list, schema, num_chunks, columns, max_errors)
+
+
+def deserialize_binary_array_tolerant(array, schema, num_chunks, *, columns=None, max_errors=1024):
+    """Extension.  ``deserialize_binary_array`` in the tolerant form: ``(list[RecordBatch], errors)``."""
+    if isinstance(array, pa.ChunkedArray):
+        array = array.combine_chunks() if array.num_chunks != 1 else array.chunk(0)
+    if not isinstance(array, (pa.BinaryArray, pa.LargeBinaryArray)):
+        raise TypeError("argument 'array': expected a pyarrow BinaryArray or LargeBinaryArray")
+    return _decode_tolerant(array, schema, num_chunks, columns, max_errors)
+
+
 def _encode(data, schema: str, num_chunks: int, want_stats: bool = False, device: int = -1, stream: int = 0):
     import ctypes
     comp = _get_schema(schema)                 # (always the full schema: projection is decode only)
@@ -284,12 +354,15 @@ def device_count() -> int:
     return _require_native().device_count()
 
 
-def deserialize_to_device(records, schema, num_chunks, device: int = -1, stream: int = 0, *, columns=None):
+def deserialize_to_device(records, schema, num_chunks, device: int = -1, stream: int = 0, *, columns=None, on_error="raise",
+                          max_errors=1024):
     """Extension: the same decode with the Arrow buffers left in HBM, every buffer a DLPack producer
     (``torch.from_dlpack(dec.batches[0].column("created_at").values)`` is an int64 tensor over the engine's memory, no copy).
-    See ``pyruhvro_amd.device``."""
+    ``on_error="placeholder"``: the tolerant form -- the result's ``.errors`` lists the malformed records that were replaced by
+    ``placeholder_datum(schema)``; with ``"raise"`` (the default) ``.errors`` is ``[]``.  See ``pyruhvro_amd.device``."""
     from .device import deserialize_to_device as f
-    return f(records, schema, num_chunks, device=device, stream=stream, kernel=_kernel_mode, columns=columns)
+    return f(records, schema, num_chunks, device=device, stream=stream, kernel=_kernel_mode, columns=columns, on_error=on_error,
+             max_errors=max_errors)
 
 
 def kernels_ready(schema: str, encode: bool = False, timeout_ms: int = 0, *, columns=None) -> bool:
@@ -312,4 +385,13 @@ __all__ = [
     "serialize_record_batch_with_stats",
     "serialize_record_batch", "serialize_record_batch_spawn", "arrow_schema", "device_count", "set_kernel_mode",
     "deserialize_binary_array", "set_devices", "kernels_ready", "prebuild", "deserialize_to_device",
+    "placeholder_datum", "validate_records", "RecordError", "deserialize_array_tolerant", "deserialize_array_threaded_tolerant",
+    "deserialize_binary_array_tolerant",
 ]
+
+
+def __getattr__(name):      # (RecordError lives beside the ctypes wrappers that build it; cabi needs numpy, imported on first use)
+    if name == "RecordError":
+        from .cabi import RecordError
+        return RecordError
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

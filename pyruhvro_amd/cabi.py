@@ -8,6 +8,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+from collections import namedtuple
 from typing import List, Optional
 
 import numpy as np
@@ -139,12 +140,27 @@ def lib():
         L.rh_device_encoded_free.argtypes = [C.c_void_p]
         L.rh_engine_counters.restype = C.c_uint32
         L.rh_engine_counters.argtypes = [C.POINTER(C.c_uint64), C.c_uint32]
+        # tolerant decode (no ABI version bump: present in every build that has it)
+        L.rh_schema_placeholder.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
+        L.rh_record_errors_count.restype = C.c_uint64
+        L.rh_record_errors_count.argtypes = [C.c_void_p]
+        L.rh_record_errors_get.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_int), C.POINTER(C.c_char_p)]
+        L.rh_record_errors_free.argtypes = [C.c_void_p]
+        L.rh_validate.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(RhOpts), C.c_uint64,
+                                  C.POINTER(C.c_void_p), C.POINTER(C.c_uint64), C.POINTER(C.c_char_p)]
+        L.rh_validate_packed.argtypes = L.rh_validate.argtypes
+        L.rh_validate_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.POINTER(RhOpts), C.c_uint64,
+                                         C.POINTER(C.c_void_p), C.POINTER(C.c_uint64), C.POINTER(C.c_char_p)]
+        L.rh_decode_tolerant.argtypes = L.rh_decode.argtypes + [C.c_uint64, C.POINTER(C.c_void_p)]
+        L.rh_decode_packed_tolerant.argtypes = L.rh_decode_tolerant.argtypes
+        L.rh_decode_device_tolerant.argtypes = L.rh_decode_device.argtypes + [C.c_uint64, C.POINTER(C.c_void_p)]
         _lib = L
     return _lib
 
 
 ENGINE_COUNTERS = ("fused_calls", "two_sync_calls", "capacity_retries", "wide_fallbacks", "offset32_errors", "split_calls", "single_pass_calls", "single_pass_failovers", "background_compiles",
-                   "tiles", "careful_tiles", "over_window_tiles", "rewalked_waves", "subtiled_tiles", "ranged_retries")
+                   "tiles", "careful_tiles", "over_window_tiles", "rewalked_waves", "subtiled_tiles", "ranged_retries",
+                   "tolerant_calls", "tolerant_repairs")
 
 
 def engine_counters() -> dict:
@@ -350,8 +366,109 @@ def decode_slices(ptrs: np.ndarray, lens: np.ndarray, schema_json: str, num_chun
     return (out, st.as_dict()) if want_stats else out
 
 
+# One malformed record of a tolerant / validation call: its index in the call's input and the message the strict call raises
+# when that record is the lowest failing one.
+RecordError = namedtuple("RecordError", ["index", "message"])
+
+
+def placeholder_datum(schema_json: str) -> bytes:
+    """rh_schema_placeholder: the datum a tolerant call puts in the place of a malformed record."""
+    p, n = C.c_void_p(), C.c_uint64()
+    if lib().rh_schema_placeholder(Schema.get(schema_json).handle, C.byref(p), C.byref(n)) != RH_OK:
+        raise RuntimeError("rh_schema_placeholder failed")
+    return C.string_at(p, n.value) if n.value else b""
+
+
+def _take_errors(handle: C.c_void_p) -> list:
+    """An rh_record_errors list -> [RecordError]; frees the list."""
+    L = lib()
+    if not handle.value:
+        return []
+    try:
+        out = []
+        idx, code, msg = C.c_uint64(), C.c_int(), C.c_char_p()
+        for i in range(L.rh_record_errors_count(handle)):
+            if L.rh_record_errors_get(handle, i, C.byref(idx), C.byref(code), C.byref(msg)) != RH_OK:
+                raise RuntimeError("rh_record_errors_get failed")
+            out.append(RecordError(int(idx.value), msg.value.decode("utf-8", "replace")))
+        return out
+    finally:
+        L.rh_record_errors_free(handle)
+
+
+def _validate(fn, lead, schema_json: str, max_errors: int, device: int, devices=None, stream=None, want_total: bool = False):
+    s = Schema.get(schema_json)
+    out, total, err = C.c_void_p(), C.c_uint64(), C.c_char_p()
+    opts, _keep = make_opts(device, 0, stream, devices)
+    rc = fn(s.handle, *lead, C.byref(opts), max_errors, C.byref(out), C.byref(total), C.byref(err))
+    if rc != RH_OK:
+        _raise(rc, err)
+    errors = _take_errors(out)
+    return (errors, int(total.value)) if want_total else errors
+
+
+def validate_packed(data: np.ndarray, offsets: np.ndarray, schema_json: str, max_errors: int = 1024, device: int = -1,
+                    devices=None, want_total: bool = False):
+    """rh_validate_packed -> [RecordError] of ALL malformed records (the max_errors lowest when there are more); with
+    want_total also their exact number."""
+    data = np.ascontiguousarray(data, dtype=np.uint8)
+    offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+    return _validate(lib().rh_validate_packed, (data.ctypes.data, offsets.ctypes.data, len(offsets) - 1), schema_json, max_errors,
+                     device, devices, None, want_total)
+
+
+def validate_slices(ptrs: np.ndarray, lens: np.ndarray, schema_json: str, max_errors: int = 1024, device: int = -1,
+                    devices=None, want_total: bool = False):
+    """rh_validate: one (pointer, length) pair per record."""
+    ptrs = np.ascontiguousarray(ptrs, dtype=np.uint64)
+    lens = np.ascontiguousarray(lens, dtype=np.uint64)
+    return _validate(lib().rh_validate, (ptrs.ctypes.data, lens.ctypes.data, len(ptrs)), schema_json, max_errors, device, devices,
+                     None, want_total)
+
+
+def validate_device(d_data: int, d_offsets: int, data_len: int, n: int, schema_json: str, max_errors: int = 1024, device: int = -1,
+                    stream: int = 0, want_total: bool = False):
+    """rh_validate_device on raw device pointers."""
+    return _validate(lib().rh_validate_device, (d_data, d_offsets, data_len, n), schema_json, max_errors, device, None, stream,
+                     want_total)
+
+
+def _decode_host_tolerant(fn, a, b, n, schema_json, num_chunks, device, kernel, devices, columns, max_errors, flags=0):
+    L = lib()
+    s = Schema.get(schema_json, columns)
+    k = L.rh_clamp_chunks(n, num_chunks)
+    arr = (ArrowArray * k)()
+    out_k, st, err, errs = C.c_uint32(), RhStats(), C.c_char_p(), C.c_void_p()
+    opts, _keep = make_opts(device, kernel | flags, None, devices)
+    rc = fn(s.handle, a, b, n, num_chunks, C.byref(opts), arr, C.byref(out_k), C.byref(st), C.byref(err), max_errors, C.byref(errs))
+    if rc != RH_OK:
+        _raise(rc, err)
+    return _import_chunks(arr, out_k.value, s.arrow_schema), _take_errors(errs)
+
+
+def decode_packed_tolerant(data: np.ndarray, offsets: np.ndarray, schema_json: str, num_chunks: int, device: int = -1,
+                           kernel: int = 0, devices=None, *, columns=None, max_errors: int = 1024, flags: int = 0):
+    """rh_decode_packed_tolerant -> (list[RecordBatch], [RecordError]): the strict call's batches with the placeholder datum in
+    the place of every malformed record, and all of those records."""
+    data = np.ascontiguousarray(data, dtype=np.uint8)
+    offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+    return _decode_host_tolerant(lib().rh_decode_packed_tolerant, data.ctypes.data, offsets.ctypes.data, len(offsets) - 1,
+                                 schema_json, num_chunks, device, kernel, devices, columns, max_errors, flags)
+
+
+def decode_slices_tolerant(ptrs: np.ndarray, lens: np.ndarray, schema_json: str, num_chunks: int, device: int = -1,
+                           kernel: int = 0, devices=None, *, columns=None, max_errors: int = 1024, flags: int = 0):
+    """rh_decode_tolerant: one (pointer, length) pair per record -> (list[RecordBatch], [RecordError])."""
+    ptrs = np.ascontiguousarray(ptrs, dtype=np.uint64)
+    lens = np.ascontiguousarray(lens, dtype=np.uint64)
+    return _decode_host_tolerant(lib().rh_decode_tolerant, ptrs.ctypes.data, lens.ctypes.data, len(ptrs), schema_json, num_chunks,
+                                 device, kernel, devices, columns, max_errors, flags)
+
+
 class DeviceResult:
     """Owns an rh_device_result (Arrow buffers resident in HBM)."""
+
+    errors: list = []      # a tolerant call's malformed records (decode_device_tolerant); [] for a strict call
 
     def __init__(self, handle, schema: Schema, stats: dict):
         self.handle = handle
@@ -492,6 +609,25 @@ def decode_device(d_data: int, d_offsets: int, data_len: int, n: int, schema_jso
         _raise(rc, err)
     r = DeviceResult(out.value, s, st.as_dict())
     r._want_stats = want_stats
+    return r
+
+
+def decode_device_tolerant(d_data: int, d_offsets: int, data_len: int, n: int, schema_json: str, num_chunks: int,
+                           device: int = -1, stream: int = 0, want_stats: bool = True, kernel: int = KERNEL_AUTO,
+                           chunk_rows: int = 0, *, columns=None, max_errors: int = 1024, flags: int = 0) -> DeviceResult:
+    """rh_decode_device_tolerant: decode_device with the placeholder datum in the place of every malformed record; the
+    result's `.errors` lists those records.  A repaired call's result owns the patched input it decoded."""
+    L = lib()
+    s = Schema.get(schema_json, columns)
+    out, st, err, errs = C.c_void_p(), RhStats(), C.c_char_p(), C.c_void_p()
+    opts, _keep = make_opts(device, kernel | flags, stream, None, chunk_rows)
+    rc = L.rh_decode_device_tolerant(s.handle, d_data, d_offsets, data_len, n, num_chunks, C.byref(opts), C.byref(out),
+                                     C.byref(st) if want_stats else None, C.byref(err), max_errors, C.byref(errs))
+    if rc != RH_OK:
+        _raise(rc, err)
+    r = DeviceResult(out.value, s, st.as_dict())
+    r._want_stats = want_stats
+    r.errors = _take_errors(errs)
     return r
 
 

@@ -101,7 +101,7 @@ struct rh_decode_call {
     uint64_t b = c * bpc64 + (rec - c * r.sz) / tile;
     rh::ErrInfo ei;
     HIPCHK(hipMemcpy(&ei, P.errinfo + b, sizeof ei, hipMemcpyDeviceToHost));
-    throw DecodeError(format_error(ei));
+    throw RecordDecodeError(format_error(ei));
   }
 
   // A call without a size pass (a schema without counters): its emit kernels counted the tiles past the window they walked

@@ -77,6 +77,9 @@ struct HipError : std::runtime_error {
 struct DecodeError : std::runtime_error {
   using std::runtime_error::runtime_error;
 };
+struct RecordDecodeError : DecodeError {       // ... of ONE record (check_bad): what a tolerant call repairs (engine_tolerant.cpp)
+  using DecodeError::DecodeError;
+};
 struct ValueClassError : std::runtime_error {   // data-dependent failures of other paths (encode): ValueError in Python
   using std::runtime_error::runtime_error;
 };
@@ -382,6 +385,9 @@ struct rh_schema {
   // Tiles past the LDS window: calls of this schema that still launch the ranged kernels behind the size / emit kernels -- set to
   // kRangedKeep by every settled call that met such tiles (the call's tile statistics: control words 8..11, summed by the scan launch), counted down by the others.
   std::atomic<uint32_t> ranged_calls{0};
+  // Tolerant decode: the schema's placeholder datum (engine_tolerant.cpp placeholder_datum), built on first use under `mu`
+  std::vector<uint8_t> placeholder;
+  bool placeholder_done = false;
   uint32_t single_cooldown = 0, single_backoff = 0;      // calls the single pass sits out after a fail-over (8, 16, ... 1024; a success clears it)
 };
 
@@ -514,6 +520,9 @@ struct rh_device_result {
   // cs / device / n / k / sz / rows_last / fail are then unused.
   std::vector<std::unique_ptr<rh_device_result>> parts;
   std::vector<uint32_t> part_chunk0;
+  // A tolerant call that repaired its input (rh_decode_device_tolerant): the patched payload and offsets the call decoded.
+  // Nothing in the result points into them; they are kept so that the result owns every byte its call read.
+  rhe::Lease patched_data, patched_offsets;
   std::vector<hipEvent_t> join_events;  // recorded on the internal streams, waited for by the caller's stream (recycled on free)
 
   rh_device_result();

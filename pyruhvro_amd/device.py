@@ -245,6 +245,7 @@ class DeviceDecode:
         self._result = result
         self.schema = schema
         self.stats = result.stats
+        self.errors = list(result.errors)      # on_error="placeholder": the malformed records that were replaced
         self.device = 0
         self.batches: List[DeviceBatch] = []
         L = cabi.lib()
@@ -274,6 +275,14 @@ class DeviceDecode:
         self._result = None           # (DLPack views hold their own reference)
 
 
+def check_max_errors(max_errors) -> int:
+    if not isinstance(max_errors, int) or isinstance(max_errors, bool):
+        raise TypeError("argument 'max_errors': expected int")
+    if max_errors < 0:
+        raise OverflowError("can't convert negative int to unsigned")
+    return max_errors
+
+
 def _pack(records) -> tuple:
     """(payload uint8[...], offsets uint64[n + 1]) from a list of bytes-like objects or a pyarrow (Large)BinaryArray."""
     if isinstance(records, pa.ChunkedArray):
@@ -296,14 +305,20 @@ def _pack(records) -> tuple:
     return np.frombuffer(b"".join(records), dtype=np.uint8), offs
 
 
-def deserialize_to_device(records, schema: str, num_chunks: int, device: int = -1, stream: int = 0, kernel: int = 0, *, columns=None) -> DeviceDecode:
+def deserialize_to_device(records, schema: str, num_chunks: int, device: int = -1, stream: int = 0, kernel: int = 0, *, columns=None,
+                          on_error: str = "raise", max_errors: int = 1024) -> DeviceDecode:
     """Extension.  Decode like ``deserialize_array_threaded(records, schema, num_chunks)`` but leave the Arrow
     buffers in HBM.  ``records``: a list of ``bytes``, a pyarrow ``BinaryArray`` / ``LargeBinaryArray`` (packed on the host and
     uploaded once), or a pair ``(data, offsets)`` of device arrays that already hold the packed payload and its n + 1 uint64
     offsets (anything with ``data_ptr()`` -- torch tensors -- or raw integer addresses; ``data`` 16-byte aligned with 64 readable
     bytes of slack).  ``stream``: the HIP stream to launch on (e.g. ``torch.cuda.current_stream().cuda_stream``).
     ``columns``: only these top-level fields, in this order (the other columns get no device buffers at all).
-    Errors are the reference's: ``ValueError`` with its message for a malformed datum or an unsupported schema."""
+    Errors are the reference's: ``ValueError`` with its message for a malformed datum or an unsupported schema.
+    ``on_error="placeholder"``: a malformed record does not abort the call; it is replaced by ``placeholder_datum(schema)`` and
+    listed in the result's ``.errors`` (``[RecordError(index, message)]``, ascending; at most ``max_errors``, beyond which the
+    call raises as with ``"raise"``)."""
+    if on_error not in ("raise", "placeholder"):
+        raise ValueError("on_error: expected 'raise' or 'placeholder'")
     if not isinstance(num_chunks, int) or isinstance(num_chunks, bool):
         raise TypeError("argument 'num_chunks': expected int")
     if num_chunks < 0:
@@ -330,7 +345,11 @@ def deserialize_to_device(records, schema: str, num_chunks: int, device: int = -
         p_data, p_off = md.ptr.value, mo.ptr.value
         keep = [md, mo]
     try:
-        r = cabi.decode_device(p_data, p_off, data_len, n, schema, num_chunks, device=device, stream=stream, kernel=kernel, columns=columns)
+        if on_error == "placeholder":
+            r = cabi.decode_device_tolerant(p_data, p_off, data_len, n, schema, num_chunks, device=device, stream=stream, kernel=kernel,
+                                            columns=columns, max_errors=check_max_errors(max_errors))
+        else:
+            r = cabi.decode_device(p_data, p_off, data_len, n, schema, num_chunks, device=device, stream=stream, kernel=kernel, columns=columns)
     finally:
         for k in keep:
             if isinstance(k, _DevMem):
