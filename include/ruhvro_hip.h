@@ -58,6 +58,29 @@ void rh_schema_free(rh_schema* s);
  * Added WITHOUT a change of RH_ABI_VERSION (7): a caller discovers it by the presence of the symbol (dlsym). */
 rh_schema* rh_schema_project(const rh_schema* s, const char* const* names, uint32_t n_names, char** err);
 
+/* Reader schemas (strict decode only).  A new, independent, immutable rh_schema that decodes records WRITTEN with `writer`
+ * into the columns of the Avro schema `reader_json` (Avro 1.11 "Schema Resolution", restricted): every decode entry point
+ * returns, buffer for buffer and with the reader's Arrow schema (field metadata included), what a plain decode under the
+ * reader schema gives for the same values as a writer of the reader schema would have encoded them.
+ *   top level:  both records have the same unqualified name; fields are matched by name only (no aliases); a writer field the
+ *               reader lacks is walked and not built; columns are in the reader's order; a reader field the writer lacks
+ *               needs a `default` -- null (a union whose first branch is null), boolean, int, long, float, double, string,
+ *               bytes or an enum symbol; a union default belongs to the first branch -- and holds it in every row.
+ *   any depth:  promotions int -> long / float / double, long -> float / double, float -> double (the C cast: one rounding),
+ *               string <-> bytes (the Arrow type only).  Everything else must match structurally (nested records field for
+ *               field, enums symbol for symbol, union branches place for place).
+ * NULL and a message that starts with "reader schema: " and names the field for anything else: a missing or unsupported
+ * default (record / array / map / fixed), nested record evolution, a union against a non-union, differing enum symbols, a
+ * pair that is no promotion.  A malformed record raises the plain `writer` decode's message for the lowest failing record,
+ * also when the damage is in a field the reader lacks.  `writer` is a schema of rh_schema_compile.  The result has its own
+ * size history and specialised kernels and is accepted by rh_schema_export, rh_decode, rh_decode_packed, rh_decode_device
+ * (RH_ASYNC and the multi-device forms included; RH_SINGLE_PASS runs the fused kernel, which handles the new ops, with the
+ * same buffers), rh_schema_prebuild, rh_schema_kernels_ready, rh_schema_kernel_source and rh_schema_kernel_key.  rh_encode*,
+ * rh_validate*, rh_decode*_tolerant and rh_schema_placeholder refuse it with RH_ERR_ARGUMENT.  A reader text equal to the
+ * writer's gives a plain compile of the writer.  Free it with rh_schema_free; it does not reference `writer`.
+ * Added WITHOUT a change of RH_ABI_VERSION (7): a caller discovers it by the presence of the symbol (dlsym). */
+rh_schema* rh_schema_resolve(const rh_schema* writer, const char* reader_json, size_t len, char** err);
+
 /* Arrow schema of the produced batches, exported as a "+s" struct schema whose
  * children are the batch columns (what arrow-rs hands pyarrow at
  * src/lib.rs:70,88 through its pyarrow FFI).  Caller releases out->release. */

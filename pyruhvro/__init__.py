@@ -1,7 +1,8 @@
 """Drop-in module name: ``import pyruhvro`` resolves to the MI355X-native engine.
 
 Same five functions as the reference's PyO3 module (src/lib.rs:150-158); the three decode functions also take the
-keyword-only extension ``columns=[...]`` (decode only those top-level fields).  Beside them the tolerant decode: the
+keyword-only extensions ``columns=[...]`` (decode only those top-level fields) and ``reader_schema=`` (decode
+writer-encoded records into an evolved schema).  Beside them the tolerant decode: the
 ``*_tolerant`` functions replace malformed records by ``placeholder_datum(schema)`` and report all of them."""
 from pyruhvro_amd import (  # noqa: F401
     deserialize_array_tolerant,

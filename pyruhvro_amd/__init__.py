@@ -65,19 +65,26 @@ def _check_columns(columns):
     return check_columns(columns)
 
 
-def _get_schema(schema: str, columns=None) -> _Compiled:
-    """The compiled schema, or -- `columns`: a tuple of distinct top-level field names -- its projection onto those columns
-    (cached by (schema string, columns): a projection is a schema of its own, with its own kernels and size history)."""
+def _get_schema(schema: str, columns=None, reader_schema=None) -> _Compiled:
+    """The compiled schema, or -- `columns`: a tuple of distinct top-level field names -- its projection onto those columns,
+    or -- `reader_schema`: Avro JSON -- the writer schema `schema` resolved into that reader schema, `columns` then naming
+    reader fields (cached by (schema, reader_schema, columns): each is a schema of its own, with its own kernels and size
+    history)."""
     if not isinstance(schema, str):
         raise TypeError("argument 'schema': expected str")
     columns = _check_columns(columns)         # ValueError before any native work
-    key = schema if columns is None else (schema, columns)
+    if reader_schema is not None and not isinstance(reader_schema, str):
+        raise TypeError("argument 'reader_schema': expected str or None")
+    key = (schema if columns is None else (schema, columns)) if reader_schema is None else (schema, reader_schema, columns)
     with _cache_lock:
         hit = _cache.get(key)
     if hit is not None:
         return hit
     nat = _require_native()
-    if columns is None:
+    if reader_schema is not None:
+        from .cabi import reader_columns
+        cap = nat.resolve_schema(_get_schema(schema).capsule, reader_columns(reader_schema, columns))   # ValueError "reader schema: ..."
+    elif columns is None:
         cap = nat.compile_schema(schema)      # ValueError on a bad / unsupported schema (src/lib.rs:52)
     else:
         cap = nat.project_schema(_get_schema(schema).capsule, columns)   # ValueError: unknown / dotted name
@@ -91,10 +98,10 @@ def _get_schema(schema: str, columns=None) -> _Compiled:
         return _cache.setdefault(key, comp)
 
 
-def arrow_schema(schema: str, *, columns=None) -> pa.Schema:
+def arrow_schema(schema: str, *, columns=None, reader_schema=None) -> pa.Schema:
     """Arrow schema the decode produces for this Avro schema (schema_translate.rs:19-37); `columns`: of the projection
-    onto those top-level fields, in that order."""
-    return _get_schema(schema, columns).arrow_schema
+    onto those top-level fields, in that order; `reader_schema`: of the decode of `schema`-written records into it."""
+    return _get_schema(schema, columns, reader_schema).arrow_schema
 
 
 KERNEL_AUTO, KERNEL_GENERIC, KERNEL_SPECIALIZED = 0, 1, 2
@@ -147,8 +154,9 @@ def _current_devices():
     return _devices if _devices is not None else _env_devices()
 
 
-def _decode(list_, schema: str, num_chunks: int, want_stats: bool = False, device: int = -1, stream: int = 0, columns=None):
-    comp = _get_schema(schema, columns)
+def _decode(list_, schema: str, num_chunks: int, want_stats: bool = False, device: int = -1, stream: int = 0, columns=None,
+            reader_schema=None):
+    comp = _get_schema(schema, columns, reader_schema)
     nat = _require_native()
     if not isinstance(num_chunks, int) or isinstance(num_chunks, bool):
         raise TypeError("argument 'num_chunks': expected int")
@@ -169,29 +177,34 @@ def _decode(list_, schema: str, num_chunks: int, want_stats: bool = False, devic
     return out, stats
 
 
-def deserialize_array(list, schema, *, columns=None):  # noqa: A002 - the reference's parameter name
+def deserialize_array(list, schema, *, columns=None, reader_schema=None):  # noqa: A002 - the reference's parameter name
     """src/lib.rs:56-71 -> ruhvro::deserialize::per_datum_deserialize (deserialize.rs:25-30).
 
     ``columns`` (keyword only, an extension): decode only these top-level fields, in this order -- the batch equals the
     full decode's ``.select(columns)`` buffer for buffer; the other columns are neither built nor copied.  A malformed
-    record still raises the full decode's error, whichever field it damages."""
-    return _decode(list, schema, 1, columns=columns)[0][0]
+    record still raises the full decode's error, whichever field it damages.
+
+    ``reader_schema`` (keyword only, an extension): ``schema`` is the schema the records were WRITTEN with and the batch is
+    in this Avro schema -- fields matched by name, writer fields it lacks dropped, fields the writer lacks filled with their
+    ``default``, columns in its order, int / long / float promoted, string <-> bytes (DESIGN.md 13 for the rules and what is
+    refused, with a ``ValueError`` that starts with ``reader schema:``).  ``columns`` then names reader fields."""
+    return _decode(list, schema, 1, columns=columns, reader_schema=reader_schema)[0][0]
 
 
-def deserialize_array_threaded(list, schema, num_chunks, *, columns=None):  # noqa: A002
+def deserialize_array_threaded(list, schema, num_chunks, *, columns=None, reader_schema=None):  # noqa: A002
     """src/lib.rs:73-89 -> per_datum_deserialize_threaded (deserialize.rs:76-121):
-    ``clamp(num_chunks, 1, max(len(list), 1))`` batches, chunk order preserved.  ``columns``: see deserialize_array."""
-    return _decode(list, schema, num_chunks, columns=columns)[0]
+    ``clamp(num_chunks, 1, max(len(list), 1))`` batches, chunk order preserved.  ``columns`` / ``reader_schema``: see deserialize_array."""
+    return _decode(list, schema, num_chunks, columns=columns, reader_schema=reader_schema)[0]
 
 
-def deserialize_array_threaded_spawn(list, schema, num_chunks, *, columns=None):  # noqa: A002
+def deserialize_array_threaded_spawn(list, schema, num_chunks, *, columns=None, reader_schema=None):  # noqa: A002
     """src/lib.rs:108-128 -- same results as deserialize_array_threaded (deserialize.rs:127-170)."""
-    return _decode(list, schema, num_chunks, columns=columns)[0]
+    return _decode(list, schema, num_chunks, columns=columns, reader_schema=reader_schema)[0]
 
 
-def deserialize_array_threaded_with_stats(list, schema, num_chunks, device: int = -1, *, columns=None):  # noqa: A002
+def deserialize_array_threaded_with_stats(list, schema, num_chunks, device: int = -1, *, columns=None, reader_schema=None):  # noqa: A002
     """Extension: also returns the engine's per-stage timings (rh_stats)."""
-    return _decode(list, schema, num_chunks, want_stats=True, device=device, columns=columns)
+    return _decode(list, schema, num_chunks, want_stats=True, device=device, columns=columns, reader_schema=reader_schema)
 
 
 def last_decode_profile():
@@ -201,7 +214,7 @@ def last_decode_profile():
     return _native.last_decode_profile()
 
 
-def deserialize_binary_array(array, schema, num_chunks, *, columns=None):
+def deserialize_binary_array(array, schema, num_chunks, *, columns=None, reader_schema=None):
     """Extension: the same decode for records that already sit in an Arrow
     ``BinaryArray`` / ``LargeBinaryArray`` (one record per element) -- the form the reference packs its
     list into internally (deserialize.rs:90).  Zero-copy on the payload: no per-``bytes`` extraction
@@ -218,7 +231,7 @@ def deserialize_binary_array(array, schema, num_chunks, *, columns=None):
         raise TypeError("argument 'num_chunks': expected int")
     if num_chunks < 0:
         raise OverflowError("can't convert negative int to unsigned")
-    _get_schema(schema, columns)                         # ValueError on a bad / unsupported schema, like every entry point
+    _get_schema(schema, columns, reader_schema)          # ValueError on a bad / unsupported schema, like every entry point
     n = len(array)
     bufs = array.buffers()
     odt = np.int64 if isinstance(array, pa.LargeBinaryArray) else np.int32
@@ -228,7 +241,8 @@ def deserialize_binary_array(array, schema, num_chunks, *, columns=None):
     data = (np.frombuffer(bufs[2], dtype=np.uint8, count=end)[base:] if bufs[2] is not None and end > base
             else np.zeros(1, dtype=np.uint8))
     offsets = (offs.astype(np.uint64) - np.uint64(base)) if n else np.zeros(1, dtype=np.uint64)
-    return cabi.decode_packed(data, offsets, schema, num_chunks, kernel=_kernel_mode, devices=_current_devices(), columns=columns)
+    return cabi.decode_packed(data, offsets, schema, num_chunks, kernel=_kernel_mode, devices=_current_devices(), columns=columns,
+                              reader_schema=reader_schema)
 
 
 def _check_chunks(num_chunks):
@@ -258,18 +272,20 @@ def placeholder_datum(schema) -> bytes:
     return cabi.placeholder_datum(schema)
 
 
-def validate_records(list, schema, *, max_errors=1024):  # noqa: A002
+def validate_records(list, schema, *, max_errors=1024, reader_schema=None):  # noqa: A002
     """Extension.  ALL malformed records of the list as ``[RecordError(index, message)]``, ascending by index (the ``max_errors``
     lowest when there are more): ``message`` is what ``deserialize_array`` raises when that record is the first malformed one."""
     from . import cabi
     from .device import check_max_errors
+    cabi.refuse_reader_schema(reader_schema, "validate_records")
     _get_schema(schema)
     data, offs = _pack_records(list)
     return cabi.validate_packed(data, offs, schema, check_max_errors(max_errors), devices=_current_devices())
 
 
-def _decode_tolerant(records, schema, num_chunks, columns, max_errors):
+def _decode_tolerant(records, schema, num_chunks, columns, max_errors, reader_schema=None):
     from . import cabi
+    cabi.refuse_reader_schema(reader_schema, "a tolerant decode")
     from .device import check_max_errors
     _check_chunks(num_chunks)
     _get_schema(schema, columns)
@@ -278,31 +294,33 @@ def _decode_tolerant(records, schema, num_chunks, columns, max_errors):
                                        columns=columns, max_errors=check_max_errors(max_errors))
 
 
-def deserialize_array_tolerant(list, schema, *, columns=None, max_errors=1024):  # noqa: A002
+def deserialize_array_tolerant(list, schema, *, columns=None, max_errors=1024, reader_schema=None):  # noqa: A002
     """Extension.  ``deserialize_array`` that a malformed record does not abort: returns ``(batch, errors)`` where the batch has
     ``placeholder_datum(schema)`` decoded in the place of every malformed record (same row count) and ``errors`` lists all of
     them as ``RecordError(index, message)``.  More than ``max_errors`` malformed records raise what ``deserialize_array``
     raises.  Clean input costs what the strict call costs."""
-    batches, errors = _decode_tolerant(list, schema, 1, columns, max_errors)
+    batches, errors = _decode_tolerant(list, schema, 1, columns, max_errors, reader_schema)
     return batches[0], errors
 
 
-def deserialize_array_threaded_tolerant(list, schema, num_chunks, *, columns=None, max_errors=1024):  # noqa: A002
+def deserialize_array_threaded_tolerant(list, schema, num_chunks, *, columns=None, max_errors=1024, reader_schema=None):  # noqa: A002
     """Extension.  ``deserialize_array_threaded`` in the tolerant form: ``(list[RecordBatch], errors)``, the chunking unchanged."""
-    return _decode_tolerant(list, schema, num_chunks, columns, max_errors)
+    return _decode_tolerant(list, schema, num_chunks, columns, max_errors, reader_schema)
 
 
-def deserialize_binary_array_tolerant(array, schema, num_chunks, *, columns=None, max_errors=1024):
+def deserialize_binary_array_tolerant(array, schema, num_chunks, *, columns=None, max_errors=1024, reader_schema=None):
     """Extension.  ``deserialize_binary_array`` in the tolerant form: ``(list[RecordBatch], errors)``."""
     if isinstance(array, pa.ChunkedArray):
         array = array.combine_chunks() if array.num_chunks != 1 else array.chunk(0)
     if not isinstance(array, (pa.BinaryArray, pa.LargeBinaryArray)):
         raise TypeError("argument 'array': expected a pyarrow BinaryArray or LargeBinaryArray")
-    return _decode_tolerant(array, schema, num_chunks, columns, max_errors)
+    return _decode_tolerant(array, schema, num_chunks, columns, max_errors, reader_schema)
 
 
-def _encode(data, schema: str, num_chunks: int, want_stats: bool = False, device: int = -1, stream: int = 0):
+def _encode(data, schema: str, num_chunks: int, want_stats: bool = False, device: int = -1, stream: int = 0, reader_schema=None):
     import ctypes
+    if reader_schema is not None:
+        raise ValueError("reader schema: serialize_* does not take reader_schema= (schema resolution is strict-decode only)")
     comp = _get_schema(schema)                 # (always the full schema: projection is decode only)
     nat = _require_native()
     if isinstance(data, pa.RecordBatch):
@@ -333,21 +351,21 @@ def _encode(data, schema: str, num_chunks: int, want_stats: bool = False, device
     return out, stats
 
 
-def serialize_record_batch(data, schema, num_chunks):
+def serialize_record_batch(data, schema, num_chunks, *, reader_schema=None):
     """src/lib.rs:91-106 -> ruhvro::serialize::serialize_record_batch (serialize.rs:38-67) with the fast encoder
     (fast_encode.rs:27-53): ``clamp(num_chunks, 1, max(rows, 1))`` BinaryArrays, one Avro datum per row, columns
     matched to the schema's fields by name.  Runs on the GPU (rh_encode)."""
-    return _encode(data, schema, num_chunks)[0]
+    return _encode(data, schema, num_chunks, reader_schema=reader_schema)[0]
 
 
-def serialize_record_batch_spawn(data, schema, num_chunks):
+def serialize_record_batch_spawn(data, schema, num_chunks, *, reader_schema=None):
     """src/lib.rs:130-148 -- same results as serialize_record_batch (serialize.rs:70-99)."""
-    return _encode(data, schema, num_chunks)[0]
+    return _encode(data, schema, num_chunks, reader_schema=reader_schema)[0]
 
 
-def serialize_record_batch_with_stats(data, schema, num_chunks, device: int = -1):
+def serialize_record_batch_with_stats(data, schema, num_chunks, device: int = -1, *, reader_schema=None):
     """Extension: also returns the engine's per-stage timings (rh_stats)."""
-    return _encode(data, schema, num_chunks, want_stats=True, device=device)
+    return _encode(data, schema, num_chunks, want_stats=True, device=device, reader_schema=reader_schema)
 
 
 def device_count() -> int:
@@ -355,29 +373,29 @@ def device_count() -> int:
 
 
 def deserialize_to_device(records, schema, num_chunks, device: int = -1, stream: int = 0, *, columns=None, on_error="raise",
-                          max_errors=1024):
+                          max_errors=1024, reader_schema=None):
     """Extension: the same decode with the Arrow buffers left in HBM, every buffer a DLPack producer
     (``torch.from_dlpack(dec.batches[0].column("created_at").values)`` is an int64 tensor over the engine's memory, no copy).
     ``on_error="placeholder"``: the tolerant form -- the result's ``.errors`` lists the malformed records that were replaced by
     ``placeholder_datum(schema)``; with ``"raise"`` (the default) ``.errors`` is ``[]``.  See ``pyruhvro_amd.device``."""
     from .device import deserialize_to_device as f
     return f(records, schema, num_chunks, device=device, stream=stream, kernel=_kernel_mode, columns=columns, on_error=on_error,
-             max_errors=max_errors)
+             max_errors=max_errors, reader_schema=reader_schema)
 
 
-def kernels_ready(schema: str, encode: bool = False, timeout_ms: int = 0, *, columns=None) -> bool:
+def kernels_ready(schema: str, encode: bool = False, timeout_ms: int = 0, *, columns=None, reader_schema=None) -> bool:
     """Extension.  A schema this process has not met is decoded by the generic kernels at once while the kernels specialised
     to it compile in the background (the reference's cost of a new schema is a JSON parse, ``src/lib.rs:39-54``; a hiprtc
     compile is seconds).  True when they are there -- the next call runs on them; waits up to ``timeout_ms`` for running
     compile jobs.  Raises ``RuntimeError`` if the compile failed (calls keep working on the generic kernels)."""
-    return bool(_require_native().kernels_ready(_get_schema(schema, columns).capsule, bool(encode), int(timeout_ms)))
+    return bool(_require_native().kernels_ready(_get_schema(schema, columns, reader_schema).capsule, bool(encode), int(timeout_ms)))
 
 
-def prebuild(schema: str, *, columns=None) -> bool:
+def prebuild(schema: str, *, columns=None, reader_schema=None) -> bool:
     """Extension.  Compile this schema's specialised kernels now (all of them, side by side) and wait: for services that
     want their first batch at full speed.  The code objects land in the kernel cache (``RUHVRO_HIP_KERNEL_CACHE`` or
     ``pyruhvro_amd/_kcache``), where later processes find them.  True when nothing had to be compiled."""
-    return bool(_require_native().prebuild(_get_schema(schema, columns).capsule))
+    return bool(_require_native().prebuild(_get_schema(schema, columns, reader_schema).capsule))
 
 
 __all__ = [

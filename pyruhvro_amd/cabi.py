@@ -94,6 +94,8 @@ def lib():
         L.rh_schema_free.argtypes = [C.c_void_p]
         L.rh_schema_project.restype = C.c_void_p      # (no ABI version bump: present in every build that has projection)
         L.rh_schema_project.argtypes = [C.c_void_p, C.POINTER(C.c_char_p), C.c_uint32, C.POINTER(C.c_char_p)]
+        L.rh_schema_resolve.restype = C.c_void_p      # (likewise: present in every build that has reader schemas)
+        L.rh_schema_resolve.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t, C.POINTER(C.c_char_p)]
         L.rh_schema_export.argtypes = [C.c_void_p, C.POINTER(ArrowSchema)]
         L.rh_clamp_chunks.restype = C.c_uint32
         L.rh_clamp_chunks.argtypes = [C.c_uint64, C.c_uint64]
@@ -206,16 +208,55 @@ def check_columns(columns):
     return cols
 
 
+def check_reader_schema(reader_schema):
+    """The `reader_schema=` argument of the strict decode entry points -> None or the Avro JSON text."""
+    if reader_schema is not None and not isinstance(reader_schema, str):
+        raise TypeError("argument 'reader_schema': expected str or None")
+    return reader_schema
+
+
+def refuse_reader_schema(reader_schema, what: str):
+    """The entry points that do not resolve (tolerant decode, validation, encode) say so before any native work."""
+    if reader_schema is not None:
+        raise ValueError(f"reader schema: {what} does not take reader_schema= (schema resolution is strict-decode only)")
+
+
+def reader_columns(reader_schema: str, columns) -> str:
+    """`columns=` composed with `reader_schema=`: the reader schema with its top-level fields pruned to `columns` and put in
+    that order, so that the resolved decode equals the whole reader's decode followed by ``.select(columns)``."""
+    if columns is None:
+        return reader_schema
+    import json
+    try:
+        j = json.loads(reader_schema)
+    except ValueError as e:
+        raise ValueError(f"reader schema: Failed to parse schema from JSON: {e}") from None
+    if not isinstance(j, dict) or not isinstance(j.get("fields"), list):
+        raise ValueError("reader schema: the top-level schema must be a record")
+    by_name = {f.get("name"): f for f in j["fields"] if isinstance(f, dict)}
+    for c in columns:
+        if c not in by_name:
+            if "." in c:
+                raise ValueError(f"columns: '{c}' is a dotted path: only top-level fields can be selected")
+            raise ValueError(f"columns: unknown top-level field '{c}' of the reader schema")
+    j["fields"] = [by_name[c] for c in columns]
+    return json.dumps(j)
+
+
 class Schema:
     """Compiled schema handle (rh_schema*) + the pyarrow schema of its batches.  `columns`: the projection onto those
-    top-level fields (rh_schema_project), an independent schema with its own kernels and size history."""
+    top-level fields (rh_schema_project), an independent schema with its own kernels and size history.  `reader_schema`:
+    `schema_json` is the writer's and the batches are the reader's (rh_schema_resolve); `columns` then names reader fields."""
 
     _cache: dict = {}
 
-    def __init__(self, schema_json: str, columns=None):
+    def __init__(self, schema_json: str, columns=None, reader_schema=None):
         L = lib()
         err = C.c_char_p()
-        if columns is None:
+        if reader_schema is not None:
+            raw = reader_columns(reader_schema, columns).encode()
+            self.handle = L.rh_schema_resolve(Schema.get(schema_json).handle, raw, len(raw), C.byref(err))
+        elif columns is None:
             raw = schema_json.encode()
             self.handle = L.rh_schema_compile(raw, len(raw), C.byref(err))
         else:
@@ -230,12 +271,13 @@ class Schema:
         self.arrow_schema = pa.schema(list(st))
 
     @classmethod
-    def get(cls, schema_json: str, columns=None) -> "Schema":
+    def get(cls, schema_json: str, columns=None, reader_schema=None) -> "Schema":
         columns = check_columns(columns)
-        key = schema_json if columns is None else (schema_json, columns)
+        reader_schema = check_reader_schema(reader_schema)
+        key = (schema_json if columns is None else (schema_json, columns)) if reader_schema is None else (schema_json, reader_schema, columns)
         s = cls._cache.get(key)
         if s is None:
-            s = cls._cache[key] = cls(schema_json, columns)
+            s = cls._cache[key] = cls(schema_json, columns, reader_schema)
         return s
 
 
@@ -249,10 +291,10 @@ RH_SINGLE_PASS = 32  # rh_opts.flags: rh_decode_device prefers the single-pass f
 RH_ASYNC = 8      # rh_opts.flags: rh_decode_device returns once the call is on the stream (rh_device_result_wait settles it)
 
 
-def kernel_source(schema_json: str, columns=None) -> str:
+def kernel_source(schema_json: str, columns=None, reader_schema=None) -> str:
     """HIP source of the schema-specialised kernels (rh_schema_kernel_source)."""
     L = lib()
-    p = L.rh_schema_kernel_source(Schema.get(schema_json, columns).handle)
+    p = L.rh_schema_kernel_source(Schema.get(schema_json, columns, reader_schema).handle)
     if not p:
         raise RuntimeError("rh_schema_kernel_source failed")
     try:
@@ -261,10 +303,10 @@ def kernel_source(schema_json: str, columns=None) -> str:
         L.rh_free_string(p)
 
 
-def kernel_key(schema_json: str, encode: bool = False, columns=None) -> str:
+def kernel_key(schema_json: str, encode: bool = False, columns=None, reader_schema=None) -> str:
     """Content hash of the schema's specialised kernel pair (rh_schema_kernel_key): the kernel-cache key."""
     L = lib()
-    p = L.rh_schema_kernel_key(Schema.get(schema_json, columns).handle, 1 if encode else 0)
+    p = L.rh_schema_kernel_key(Schema.get(schema_json, columns, reader_schema).handle, 1 if encode else 0)
     if not p:
         raise RuntimeError("rh_schema_kernel_key failed")
     try:
@@ -285,23 +327,23 @@ def encode_kernel_source(schema_json: str) -> str:
         L.rh_free_string(p)
 
 
-def prebuild(schema_json: str, columns=None) -> bool:
+def prebuild(schema_json: str, columns=None, reader_schema=None) -> bool:
     """Compile the schema-specialised kernels into the on-disk kernel cache (hiprtc; no GPU needed).
     Returns True when the code object was already cached."""
     L = lib()
     cached = C.c_int()
     err = C.c_char_p()
-    rc = L.rh_schema_prebuild(Schema.get(schema_json, columns).handle, C.byref(cached), C.byref(err))
+    rc = L.rh_schema_prebuild(Schema.get(schema_json, columns, reader_schema).handle, C.byref(cached), C.byref(err))
     if rc != RH_OK:
         _raise(rc, err)
     return bool(cached.value)
 
 
-def kernels_ready(schema_json: str, encode: bool = False, timeout_ms: int = 0, columns=None) -> bool:
+def kernels_ready(schema_json: str, encode: bool = False, timeout_ms: int = 0, columns=None, reader_schema=None) -> bool:
     """rh_schema_kernels_ready: True when the schema's specialised kernels are there (the next call runs on them), False while
     their compile jobs are still running after `timeout_ms` (or nobody asked for them); raises when the compile failed."""
     err = C.c_char_p()
-    rc = lib().rh_schema_kernels_ready(Schema.get(schema_json, columns).handle, 1 if encode else 0, int(timeout_ms), C.byref(err))
+    rc = lib().rh_schema_kernels_ready(Schema.get(schema_json, columns, reader_schema).handle, 1 if encode else 0, int(timeout_ms), C.byref(err))
     if rc < 0:
         _raise(RH_ERR_RUNTIME, err)
     return rc == 1
@@ -315,12 +357,12 @@ def shard_chunks(n: int, num_chunks: int, n_shards: int, shard: int):
 
 
 def decode_packed(data: np.ndarray, offsets: np.ndarray, schema_json: str, num_chunks: int,
-                  device: int = -1, want_stats: bool = False, kernel: int = KERNEL_AUTO, devices=None, *, columns=None):
+                  device: int = -1, want_stats: bool = False, kernel: int = KERNEL_AUTO, devices=None, *, columns=None, reader_schema=None):
     """rh_decode_packed: one contiguous payload + u64 offsets (host memory) -> list[RecordBatch].
     `devices`: shard the chunks over these HIP devices (rh_opts.devices); with want_stats the stats dict then carries
     the per-shard stats under "device_stats"."""
     L = lib()
-    s = Schema.get(schema_json, columns)
+    s = Schema.get(schema_json, columns, reader_schema)
     data = np.ascontiguousarray(data, dtype=np.uint8)
     offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
     n = len(offsets) - 1
@@ -344,11 +386,11 @@ def decode_packed(data: np.ndarray, offsets: np.ndarray, schema_json: str, num_c
 
 
 def decode_slices(ptrs: np.ndarray, lens: np.ndarray, schema_json: str, num_chunks: int,
-                  device: int = -1, want_stats: bool = False, kernel: int = KERNEL_AUTO, devices=None, *, columns=None):
+                  device: int = -1, want_stats: bool = False, kernel: int = KERNEL_AUTO, devices=None, *, columns=None, reader_schema=None):
     """rh_decode: one (pointer, length) pair per record, the form the CPython boundary extracts from list[bytes]
     (u64 addresses / u64 lengths; the caller keeps the pointed-to memory alive) -> list[RecordBatch]."""
     L = lib()
-    s = Schema.get(schema_json, columns)
+    s = Schema.get(schema_json, columns, reader_schema)
     ptrs = np.ascontiguousarray(ptrs, dtype=np.uint64)
     lens = np.ascontiguousarray(lens, dtype=np.uint64)
     n = len(ptrs)
@@ -592,12 +634,12 @@ def encode_device(batch_array_addr: int, batch_schema_addr: int, schema_json: st
 def decode_device(d_data: int, d_offsets: int, data_len: int, n: int, schema_json: str, num_chunks: int,
                   device: int = -1, stream: int = 0, want_stats: bool = True, kernel: int = KERNEL_AUTO,
                   chunk_rows: int = 0, asynchronous: bool = False, two_pass: bool = False, single_pass: bool = False,
-                  *, columns=None) -> DeviceResult:
+                  *, columns=None, reader_schema=None) -> DeviceResult:
     """rh_decode_device on raw device pointers (e.g. torch tensors' data_ptr()).  chunk_rows: explicit geometry
     for a range of a larger call's chunks (rh_opts.chunk_rows).  asynchronous: RH_ASYNC -- the result is returned
     unsettled (DeviceResult.wait() settles it and fills .stats; every accessor settles implicitly)."""
     L = lib()
-    s = Schema.get(schema_json, columns)
+    s = Schema.get(schema_json, columns, reader_schema)
     out = C.c_void_p()
     st = RhStats()
     err = C.c_char_p()
@@ -639,9 +681,9 @@ class PreparedDeviceDecode:
 
     def __init__(self, d_data: int, d_offsets: int, data_len: int, n: int, schema_json: str, num_chunks: int,
                  device: int = -1, stream: int = 0, kernel: int = KERNEL_AUTO, chunk_rows: int = 0, asynchronous: bool = False,
-                 two_pass: bool = False, single_pass: bool = False, *, columns=None):
+                 two_pass: bool = False, single_pass: bool = False, *, columns=None, reader_schema=None):
         self._L = lib()
-        self._schema = Schema.get(schema_json, columns)
+        self._schema = Schema.get(schema_json, columns, reader_schema)
         self._opts, self._keep = make_opts(device, kernel | (RH_ASYNC if asynchronous else 0) | (RH_TWO_PASS if two_pass else 0) |
                                            (RH_SINGLE_PASS if single_pass else 0), stream, None, chunk_rows)
         self._wait = self._L.rh_device_result_wait

@@ -203,6 +203,23 @@ rh_schema* rh_schema_project(const rh_schema* s, const char* const* names, uint3
   return out;
 }
 
+rh_schema* rh_schema_resolve(const rh_schema* writer, const char* reader_json, size_t len, char** err) {
+  rh_schema* out = nullptr;
+  if (!writer || !reader_json) {
+    if (err) *err = dup_msg("rh_schema_resolve: null argument");
+    return nullptr;
+  }
+  guarded(err, [&] {
+    if (writer->cs->projected) throw rh::SchemaError("reader schema: the writer schema must be a plain compiled schema (not a projection or a resolution)");
+    // from the schema TEXTS: the resolution is an independent, immutable schema (own size history, own kernels)
+    auto cs = rh::compile_schema_resolved(writer->cs->json.data(), writer->cs->json.size(), reader_json, len);
+    out = new rh_schema();
+    out->cs = std::move(cs);
+    return RH_OK;
+  });
+  return out;
+}
+
 void rh_schema_free(rh_schema* s) {
   if (!s) return;
   for (auto& kv : s->dev) {
@@ -299,7 +316,7 @@ int rh_schema_kernels_ready(const rh_schema* s, int encode, long timeout_ms, cha
   if (!s) return -1;
   try {
     if (encode && s->cs->projected) {
-      if (err) *err = dup_msg("a projected schema is decode only");
+      if (err) *err = dup_msg(s->cs->resolved ? "a resolved schema is decode only" : "a projected schema is decode only");
       return -1;
     }
     const unsigned parts = encode ? rh::kEncodeParts : ((1u << rh::KP_SIZE) | (1u << rh::KP_EMIT));

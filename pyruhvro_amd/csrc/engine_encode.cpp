@@ -256,6 +256,7 @@ int encode_impl(rh_schema* s, const ArrowArray* batch, const ArrowSchema* bschem
                 ArrowArray* out_chunks, uint32_t* out_k, rh_stats* stats, rh_device_encoded** dev_out = nullptr) {
   const bool dev = dev_out != nullptr;
   const CompiledSchema& cs = *s->cs;
+  if (cs.resolved) throw std::invalid_argument("a resolved schema (rh_schema_resolve) is decode only: encode with the schema the records are to be written in");
   if (cs.projected) throw std::invalid_argument("a projected schema (rh_schema_project) is decode only: encode with the full schema");
   if (!cs.encode_unsupported.empty())
     throw rh::SchemaError("schema is outside the GPU encode path (" + cs.encode_unsupported +

@@ -346,10 +346,17 @@ static rh_device_result* decode_device_tolerant(rh_schema* s, const uint8_t* d_d
 // ===========================================================================
 // C ABI
 // ===========================================================================
+// Reader schemas (rh_schema_resolve) are strict-decode only: tolerant resolution is a follow-up
+static bool refuse_resolved(const rh_schema* s, char** err) {
+  if (!s || !s->cs->resolved) return false;
+  if (err) *err = dup_msg("a resolved schema (rh_schema_resolve) takes the strict decode entry points only: validate / decode tolerantly with the writer schema");
+  return true;
+}
+
 extern "C" {
 
 int rh_schema_placeholder(const rh_schema* s, const uint8_t** bytes, uint64_t* len) {
-  if (!s || !bytes || !len) return RH_ERR_ARGUMENT;
+  if (!s || !bytes || !len || s->cs->resolved) return RH_ERR_ARGUMENT;
   try {
     const std::vector<uint8_t>& ph = placeholder_datum(const_cast<rh_schema*>(s));
     static const uint8_t kNone = 0;
@@ -388,6 +395,7 @@ static int validate_entry(const rh_schema* s, const Source& src, uint64_t n, con
 int rh_validate(const rh_schema* s, const uint8_t* const* ptrs, const uint64_t* lens, uint64_t n, const rh_opts* opts,
                 uint64_t max_errors, rh_record_errors** out, uint64_t* total_bad, char** err) {
   if (!s || (n && (!ptrs || !lens))) return RH_ERR_ARGUMENT;
+  if (refuse_resolved(s, err)) return RH_ERR_ARGUMENT;
   Source src;
   src.ptrs = ptrs;
   src.lens = lens;
@@ -397,6 +405,7 @@ int rh_validate(const rh_schema* s, const uint8_t* const* ptrs, const uint64_t* 
 int rh_validate_packed(const rh_schema* s, const uint8_t* data, const uint64_t* offsets, uint64_t n, const rh_opts* opts,
                        uint64_t max_errors, rh_record_errors** out, uint64_t* total_bad, char** err) {
   if (!s || !offsets) return RH_ERR_ARGUMENT;
+  if (refuse_resolved(s, err)) return RH_ERR_ARGUMENT;
   Source src;
   src.data = data;
   src.offsets = offsets;
@@ -407,6 +416,7 @@ int rh_validate_device(const rh_schema* s, const void* d_data, const void* d_off
                        const rh_opts* opts, uint64_t max_errors, rh_record_errors** out, uint64_t* total_bad, char** err) {
   if (!s) return RH_ERR_ARGUMENT;
   if (out) *out = nullptr;
+  if (refuse_resolved(s, err)) return RH_ERR_ARGUMENT;
   return guarded(err, [&] {
     require_device();
     const int device = call_device(opts, false);
@@ -423,6 +433,7 @@ int rh_decode_tolerant(const rh_schema* s, const uint8_t* const* ptrs, const uin
                        const rh_opts* opts, struct ArrowArray* out_chunks, uint32_t* out_k, rh_stats* stats, char** err,
                        uint64_t max_errors, rh_record_errors** errors) {
   if (!s || !out_chunks || (n && (!ptrs || !lens))) return RH_ERR_ARGUMENT;
+  if (refuse_resolved(s, err)) return RH_ERR_ARGUMENT;
   return guarded(err, [&] {
     Source src;
     src.ptrs = ptrs;
@@ -435,6 +446,7 @@ int rh_decode_packed_tolerant(const rh_schema* s, const uint8_t* data, const uin
                               const rh_opts* opts, struct ArrowArray* out_chunks, uint32_t* out_k, rh_stats* stats, char** err,
                               uint64_t max_errors, rh_record_errors** errors) {
   if (!s || !offsets || !out_chunks) return RH_ERR_ARGUMENT;
+  if (refuse_resolved(s, err)) return RH_ERR_ARGUMENT;
   return guarded(err, [&] {
     Source src;
     src.data = data;
@@ -447,6 +459,7 @@ int rh_decode_device_tolerant(const rh_schema* s, const void* d_data, const void
                               uint64_t num_chunks, const rh_opts* opts, rh_device_result** out, rh_stats* stats, char** err,
                               uint64_t max_errors, rh_record_errors** errors) {
   if (!s || !out) return RH_ERR_ARGUMENT;
+  if (refuse_resolved(s, err)) return RH_ERR_ARGUMENT;
   return guarded(err, [&] {
     refuse_async(opts);
     require_device();

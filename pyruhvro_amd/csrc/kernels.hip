@@ -30,6 +30,7 @@
 #include "program.h"
 #include "walk.h"
 #include "walk_drop.h"
+#include "walk_resolve.h"
 
 namespace rh {
 
@@ -155,6 +156,11 @@ __device__ __forceinline__ void walk(const KParams& P, const Ctx& c, const Src& 
     if constexpr (DROP) {
       if (op.flags & F_DROP) {
         if (!run_dropped<EMIT, CAREFUL>(c, src, L, op)) { npc = op.b; nxt = ld_op(prog + npc); }
+        pc = npc;
+        continue;
+      }
+      if (op.flags & F_RESOLVE_MASK) {      // (resolved schemas, walk_resolve.h: a promoted or a defaulted leaf)
+        run_resolved<EMIT, CAREFUL>(c, src, L, op);
         pc = npc;
         continue;
       }

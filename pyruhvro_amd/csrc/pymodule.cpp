@@ -85,6 +85,20 @@ PyObject* py_project_schema(PyObject*, PyObject* args) {
   return PyCapsule_New(h, kCapsule, capsule_free);
 }
 
+// resolve_schema(capsule of the writer schema, reader schema JSON) -> capsule of the resolved schema (rh_schema_resolve)
+PyObject* py_resolve_schema(PyObject*, PyObject* args) {
+  PyObject* cap;
+  const char* r;
+  Py_ssize_t n;
+  if (!PyArg_ParseTuple(args, "Os#", &cap, &r, &n)) return nullptr;
+  rh_schema* s = get_schema(cap);
+  if (!s) return nullptr;
+  char* err = nullptr;
+  rh_schema* h = rh_schema_resolve(s, r, (size_t)n, &err);
+  if (!h) return raise_from(RH_ERR_SCHEMA, err);
+  return PyCapsule_New(h, kCapsule, capsule_free);
+}
+
 PyObject* py_schema_ptr(PyObject*, PyObject* args) {
   PyObject* cap;
   if (!PyArg_ParseTuple(args, "O", &cap)) return nullptr;
@@ -584,6 +598,7 @@ PyObject* py_last_decode_profile(PyObject*, PyObject*) {
 
 PyMethodDef methods[] = {
     {"compile_schema", py_compile_schema, METH_VARARGS, "compile_schema(json) -> schema capsule"},
+    {"resolve_schema", py_resolve_schema, METH_VARARGS, "resolve_schema(capsule, reader_json) -> capsule of the writer schema resolved into the reader schema"},
     {"project_schema", py_project_schema, METH_VARARGS, "project_schema(capsule, names) -> capsule of the schema projected onto those top-level columns"},
     {"schema_ptr", py_schema_ptr, METH_VARARGS, "schema_ptr(capsule) -> int (rh_schema*)"},
     {"export_schema", py_export_schema, METH_VARARGS, "export_schema(capsule) -> address of ArrowSchema"},

@@ -35,6 +35,8 @@ std::string kernel_cache_key(const std::string& source, bool encode) {
     if (source.find("#include \"walk_drop.h\"") != std::string::npos) h = fnv1a(kHdr_walk_drop_h, h);
     // (likewise spec_flat.h: schemas without a size pass only)
     if (source.find("#include \"spec_flat.h\"") != std::string::npos) h = fnv1a(kHdr_spec_flat_h, h);
+    // (likewise walk_resolve.h: resolved schemas only)
+    if (source.find("#include \"walk_resolve.h\"") != std::string::npos) h = fnv1a(kHdr_walk_resolve_h, h);
   }
   char buf[32];
   std::snprintf(buf, sizeof buf, "%016llx", (unsigned long long)h);
@@ -105,10 +107,10 @@ std::vector<char> compile_kernel(const std::string& source, std::string& log) {
   Rtc& r = rtc();
   if (!r.h) throw std::runtime_error("cannot specialise the decode kernel: " + r.why);
   const char* hdr_src[] = {kHdr_program_h, kHdr_walk_h, kHdr_kernel_common_h, kHdr_spec_body_h,
-                           kHdr_encode_h, kHdr_encode_walk_h, kHdr_encode_spec_h, kHdr_walk_drop_h, kHdr_spec_flat_h};
-  const char* hdr_name[] = {"program.h", "walk.h", "kernel_common.h", "spec_body.h", "encode.h", "encode_walk.h", "encode_spec.h", "walk_drop.h", "spec_flat.h"};
+                           kHdr_encode_h, kHdr_encode_walk_h, kHdr_encode_spec_h, kHdr_walk_drop_h, kHdr_spec_flat_h, kHdr_walk_resolve_h};
+  const char* hdr_name[] = {"program.h", "walk.h", "kernel_common.h", "spec_body.h", "encode.h", "encode_walk.h", "encode_spec.h", "walk_drop.h", "spec_flat.h", "walk_resolve.h"};
   void* prog = nullptr;
-  if (r.create(&prog, source.c_str(), "ruhvro_spec.hip", 9, hdr_src, hdr_name) != 0)
+  if (r.create(&prog, source.c_str(), "ruhvro_spec.hip", 10, hdr_src, hdr_name) != 0)
     throw std::runtime_error("hiprtcCreateProgram failed");
   const char* opts[] = {"--offload-arch=gfx950", "-O3", "-std=c++17", "-w"};
   const int rc = r.compile(prog, 4, opts);

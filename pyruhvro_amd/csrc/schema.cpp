@@ -1,13 +1,15 @@
 // See schema.h.  Host only (no HIP).
 #include "schema.h"
 #include <algorithm>
+#include <cerrno>
 #include <cmath>
+#include <cstring>
 
 #include <map>
 #include <set>
 
 #include "json.hpp"
-#include "walk_drop.h"
+#include "walk_resolve.h"
 
 namespace rh {
 namespace {
@@ -22,7 +24,7 @@ std::unique_ptr<AvroType> clone_type(const AvroType& t) {
   auto c = std::make_unique<AvroType>();
   c->kind = t.kind; c->name = t.name; c->ns = t.ns; c->has_doc = t.has_doc; c->doc = t.doc;
   c->has_aliases = t.has_aliases; c->aliases = t.aliases; c->symbols = t.symbols; c->logical = t.logical;
-  c->size = t.size; c->precision = t.precision; c->scale = t.scale;
+  c->size = t.size; c->precision = t.precision; c->scale = t.scale; c->wire_kind = t.wire_kind;
   for (const AvroField& f : t.fields) {
     AvroField g;
     g.name = f.name; g.has_doc = f.has_doc; g.doc = f.doc;
@@ -454,7 +456,7 @@ struct Builder {
   }
 
   static uint32_t min_bytes(const AvroType& t) {
-    switch (t.kind) {
+    switch (t.wire_kind >= 0 ? (AvroKind)t.wire_kind : t.kind) {      // (a promoted leaf of a resolved schema: what the WRITER wrote)
       case AV_NULL: return 0;
       case AV_FLOAT: return 4;
       case AV_DOUBLE: return 8;
@@ -540,6 +542,24 @@ struct Builder {
     cs.max_union_depth = std::max(cs.max_union_depth, tmp.max_union_depth);
   }
 
+  // A reader field the writer lacks (resolved schemas): the field's ordinary leaf -- node, buffers, counter as for any column -- whose
+  // op reads `datum`, the default encoded as the Avro datum of the field's type, from the symbol blob (walk_resolve.h F_CONST).
+  // An enum default is stored as its symbol text (a length and the bytes): the column is the same, and no index is looked up.
+  int build_const(const AvroType& t, const std::vector<uint8_t>& datum, const Ctx& cx) {
+    const size_t pc = cs.prog.size();
+    const int id = build(t, false, false, cx);
+    if (cs.prog.size() != pc + 1 || (cs.prog[pc].code != OP_FIXED && cs.prog[pc].code != OP_STRING && cs.prog[pc].code != OP_ENUM))
+      throw SchemaError("reader schema: internal: a default that is not a leaf");
+    Op& o = cs.prog[pc];
+    if (o.code == OP_ENUM) o.code = OP_STRING;
+    o.flags |= F_CONST;
+    o.b = (int32_t)cs.sym_data.size();
+    o.c = (int32_t)datum.size();
+    cs.sym_data.insert(cs.sym_data.end(), datum.begin(), datum.end());
+    cs.sym_data.insert(cs.sym_data.end(), kConstSlack, (uint8_t)0);
+    return id;
+  }
+
   // make_decoder / make_nullable_decoder / make_union_decoder
   int build(const AvroType& t, bool nullable, bool null_first, Ctx cx) {
     if (cx.nest > kMaxNest) throw SchemaError("schema nesting too deep for the GPU decoder");
@@ -594,6 +614,10 @@ struct Builder {
         Op o = mk(OP_FIXED);
         o.flags = (nullable ? F_NULLABLE : 0) | (null_first ? F_NULL_FIRST : 0) | (can_null ? F_CAN_NULL : 0);
         o.dom = cx.dom; o.a = fixed; o.buf0 = bv; o.buf1 = bm; o.node = id;
+        if (t.wire_kind >= 0) {      // resolved schemas (walk_resolve.h h_fixed_p): read as the writer's kind, stored as this one
+          o.a = t.wire_kind == AV_INT ? FK_I32 : t.wire_kind == AV_LONG ? FK_I64 : FK_F32;
+          o.flags |= promote_flags(fixed);
+        }
         push(o);
         return id;
       }
@@ -705,6 +729,8 @@ struct Builder {
   }
 };
 
+void finish_program(CompiledSchema& c0, Builder& b, const AvroType& wire_top);
+
 // `cols` == nullptr: every column
 std::unique_ptr<CompiledSchema> compile_impl(const char* text, size_t len, const std::vector<std::string>* cols) {
   auto cs = std::make_unique<CompiledSchema>();
@@ -775,6 +801,14 @@ std::unique_ptr<CompiledSchema> compile_impl(const char* text, size_t len, const
     }
     cs->nodes[(size_t)id].children = kids;
   }
+  finish_program(*cs, b, top);
+  return cs;
+}
+
+// The tail of every compile: OP_END, counter numbering, the bounds the engine keys on.  `wire_top`: the record as it is WRITTEN.
+void finish_program(CompiledSchema& c0, Builder& b, const AvroType& wire_top) {
+  CompiledSchema* const cs = &c0;
+  const AvroType& top = wire_top;
   cs->prog.push_back(Builder::mk(OP_END));
 
   // counters: row domains first (domain d -> counter d-1), then the string byte columns.
@@ -812,6 +846,264 @@ std::unique_ptr<CompiledSchema> compile_impl(const char* text, size_t len, const
   if (cs->sym_data.empty()) cs->sym_data.push_back(0);
   cs->min_record_bytes = Builder::min_bytes(top);
   cs->size_always = cs->projected && cs->K == 0 && b.dropped_varlen;
+}
+
+
+// ===========================================================================
+// 5. reader schemas (Avro 1.11 "Schema Resolution", restricted: DESIGN.md 13)
+// ===========================================================================
+[[noreturn]] void resolve_fail(const std::string& path, const std::string& what) {
+  throw SchemaError("reader schema: field '" + path + "': " + what);
+}
+
+const char* kind_name(AvroKind k) {
+  switch (k) {
+    case AV_NULL: return "null"; case AV_BOOLEAN: return "boolean"; case AV_INT: return "int"; case AV_LONG: return "long";
+    case AV_FLOAT: return "float"; case AV_DOUBLE: return "double"; case AV_BYTES: return "bytes"; case AV_STRING: return "string";
+    case AV_RECORD: return "record"; case AV_ENUM: return "enum"; case AV_ARRAY: return "array"; case AV_MAP: return "map";
+    case AV_UNION: return "union"; case AV_FIXED: return "fixed"; case AV_DATE: return "date"; case AV_TS_MILLIS: return "timestamp-millis";
+    case AV_TS_MICROS: return "timestamp-micros"; case AV_TIME_MILLIS: return "time-millis"; case AV_TIME_MICROS: return "time-micros";
+    case AV_DECIMAL: return "decimal"; case AV_UUID: return "uuid"; case AV_DURATION: return "duration";
+    default: return "unsupported type";
+  }
+}
+
+bool promotable(AvroKind w, AvroKind r) {
+  switch (w) {
+    case AV_INT: return r == AV_LONG || r == AV_FLOAT || r == AV_DOUBLE;
+    case AV_LONG: return r == AV_FLOAT || r == AV_DOUBLE;
+    case AV_FLOAT: return r == AV_DOUBLE;
+    case AV_STRING: return r == AV_BYTES;
+    case AV_BYTES: return r == AV_STRING;
+    default: return false;
+  }
+}
+
+// Can a value written as `w` be read as `r`?  "" = yes, else why not.  `mark`: note the writer's kind on every promoted numeric
+// leaf of `r` (AvroType::wire_kind).  Below the top level the two types match structurally, leaf promotions aside.
+std::string resolve_match(const AvroType& w, AvroType& r, const std::string& path, bool mark) {
+  auto no = [&](const std::string& what) { return "reader schema: field '" + path + "': " + what; };
+  if (w.kind == AV_UNION && r.kind == AV_UNION) {
+    if (w.variants.size() != r.variants.size())
+      return no("the reader's union has " + std::to_string(r.variants.size()) + " branches, the writer's " + std::to_string(w.variants.size()) +
+                " (adding or removing union branches is not supported)");
+    for (size_t i = 0; i < w.variants.size(); i++) {
+      size_t j = 0;
+      while (j < r.variants.size() && !resolve_match(*w.variants[i], *r.variants[j], path, false).empty()) j++;
+      if (j == r.variants.size()) return resolve_match(*w.variants[i], *r.variants[i], path + "[branch " + std::to_string(i) + "]", false);
+      if (j != i)
+        return no("writer union branch " + std::to_string(i) + " (" + kind_name(w.variants[i]->kind) + ") resolves to reader branch " + std::to_string(j) +
+                  " (" + kind_name(r.variants[j]->kind) + "), not to branch " + std::to_string(i) + ": union branches must keep their places");
+      if (mark) resolve_match(*w.variants[i], *r.variants[i], path, true);
+    }
+    return "";
+  }
+  if (w.kind == AV_UNION)
+    return no("the writer's type is a union and the reader's is not (making a field non-nullable is not supported)");
+  if (r.kind == AV_UNION)
+    return no("the reader's type is a union and the writer's is not (making a field nullable is not supported)");
+  if (w.kind != r.kind) {
+    if (!promotable(w.kind, r.kind)) return no(std::string("a writer's ") + kind_name(w.kind) + " cannot be read as " + kind_name(r.kind));
+    if (mark && w.kind != AV_STRING && w.kind != AV_BYTES) r.wire_kind = (int)w.kind;
+    return "";
+  }
+  switch (w.kind) {
+    case AV_RECORD: {
+      if (w.name != r.name) return no("the reader's record is named '" + r.name + "', the writer's '" + w.name + "'");
+      bool same = w.fields.size() == r.fields.size();
+      for (size_t i = 0; same && i < w.fields.size(); i++) same = w.fields[i].name == r.fields[i].name;
+      if (!same)
+        return no("nested record resolution is not supported (adding, dropping or reordering the fields of the nested record '" + r.name + "')");
+      for (size_t i = 0; i < w.fields.size(); i++) {
+        std::string m = resolve_match(*w.fields[i].type, *r.fields[i].type, path + "." + w.fields[i].name, mark);
+        if (!m.empty()) return m;
+      }
+      return "";
+    }
+    case AV_ENUM:
+      if (w.symbols != r.symbols) return no("the enum symbols differ (mapping enum symbols is not supported)");
+      return "";
+    case AV_FIXED:
+      if (w.name != r.name || w.size != r.size) return no("fixed types differ in name or size");
+      return "";
+    case AV_DECIMAL:
+      if (w.precision != r.precision || w.scale != r.scale || w.size != r.size) return no("decimal types differ in precision, scale or base type");
+      return "";
+    case AV_UUID:
+      if (w.size != r.size) return no("uuid types differ in base type");
+      return "";
+    case AV_ARRAY: return resolve_match(*w.items, *r.items, path + "[]", mark);
+    case AV_MAP: return resolve_match(*w.items, *r.items, path + "{}", mark);
+    default: return "";
+  }
+}
+
+void put_zigzag(std::vector<uint8_t>& out, int64_t v) {
+  uint64_t u = ((uint64_t)v << 1) ^ (uint64_t)(v >> 63);
+  while (u >= 0x80) { out.push_back((uint8_t)(u | 0x80)); u >>= 7; }
+  out.push_back((uint8_t)u);
+}
+
+// the default `d` of reader field `path` as the Avro datum of its type `t` (a union default belongs to the first branch)
+std::vector<uint8_t> encode_default(const AvroType& t, const Value& d, const std::string& path) {
+  std::vector<uint8_t> out;
+  const AvroType* v = &t;
+  if (t.kind == AV_UNION) {
+    bool nf = false;
+    if (t.variants.empty() || !Builder::null_union_inner(t, nf))
+      resolve_fail(path, "a default for a union of other than [\"null\", T] / [T, \"null\"] is not supported yet");
+    put_zigzag(out, 0);
+    v = t.variants[0].get();
+    for (auto& br : t.variants)
+      switch (br->kind) {
+        case AV_NULL: case AV_BOOLEAN: case AV_INT: case AV_DATE: case AV_TIME_MILLIS: case AV_LONG: case AV_TS_MILLIS: case AV_TS_MICROS:
+        case AV_TIME_MICROS: case AV_FLOAT: case AV_DOUBLE: case AV_STRING: case AV_BYTES: case AV_ENUM: break;
+        default: resolve_fail(path, std::string("a default for a nullable ") + kind_name(br->kind) + " is not supported yet");
+      }
+    if (v->kind == AV_NULL) {
+      if (d.type != Value::Null) resolve_fail(path, "the default of a union belongs to its first branch, which is null");
+      return out;
+    }
+  }
+  auto mismatch = [&]() { resolve_fail(path, std::string("the default does not match the field's type ") + kind_name(v->kind)); };
+  auto put_text = [&](const std::string& bytes) {
+    if (bytes.size() > kMaxDefaultBytes)
+      resolve_fail(path, "a string / bytes default of more than " + std::to_string(kMaxDefaultBytes) + " bytes is not supported yet");
+    put_zigzag(out, (int64_t)bytes.size());
+    out.insert(out.end(), bytes.begin(), bytes.end());
+  };
+  switch (v->kind) {
+    case AV_BOOLEAN:
+      if (d.type != Value::Bool) mismatch();
+      out.push_back(d.b ? 1 : 0);
+      break;
+    case AV_INT: case AV_DATE: case AV_TIME_MILLIS: case AV_LONG: case AV_TS_MILLIS: case AV_TS_MICROS: case AV_TIME_MICROS: {
+      if (!d.is_number() || d.str.find_first_of(".eE") != std::string::npos) mismatch();
+      errno = 0;
+      char* endp = nullptr;
+      const long long x = std::strtoll(d.str.c_str(), &endp, 10);
+      const bool is32 = v->kind == AV_INT || v->kind == AV_DATE || v->kind == AV_TIME_MILLIS;
+      if (errno != 0 || !endp || *endp != 0 || (is32 && (x < INT32_MIN || x > INT32_MAX))) resolve_fail(path, "the default is out of the type's range");
+      put_zigzag(out, (int64_t)x);
+      break;
+    }
+    case AV_FLOAT: {
+      if (!d.is_number()) mismatch();
+      const float f = (float)d.num;
+      uint32_t u;
+      std::memcpy(&u, &f, 4);
+      for (int i = 0; i < 4; i++) out.push_back((uint8_t)(u >> (8 * i)));
+      break;
+    }
+    case AV_DOUBLE: {
+      if (!d.is_number()) mismatch();
+      uint64_t u;
+      std::memcpy(&u, &d.num, 8);
+      for (int i = 0; i < 8; i++) out.push_back((uint8_t)(u >> (8 * i)));
+      break;
+    }
+    case AV_STRING:
+      if (!d.is_string()) mismatch();
+      put_text(d.str);
+      break;
+    case AV_BYTES: {      // a JSON string whose code points 0..255 are the bytes (the specification's form)
+      if (!d.is_string()) mismatch();
+      std::string raw;
+      for (size_t i = 0; i < d.str.size();) {
+        const uint8_t c0 = (uint8_t)d.str[i];
+        if (c0 < 0x80) { raw.push_back((char)c0); i++; continue; }
+        if ((c0 == 0xC2 || c0 == 0xC3) && i + 1 < d.str.size()) { raw.push_back((char)(((c0 & 3) << 6) | ((uint8_t)d.str[i + 1] & 0x3F))); i += 2; continue; }
+        resolve_fail(path, "a bytes default holds a code point above 255");
+      }
+      put_text(raw);
+      break;
+    }
+    case AV_ENUM: {
+      if (!d.is_string()) mismatch();
+      if (std::find(v->symbols.begin(), v->symbols.end(), d.str) == v->symbols.end())
+        resolve_fail(path, "the default '" + d.str + "' is not a symbol of the enum");
+      put_text(d.str);
+      break;
+    }
+    default:
+      resolve_fail(path, std::string("a default of type ") + kind_name(v->kind) + " is not supported yet");
+  }
+  return out;
+}
+
+std::unique_ptr<CompiledSchema> resolve_impl(const char* wtext, size_t wlen, const char* rtext, size_t rlen) {
+  auto plain = compile_impl(wtext, wlen, nullptr);      // (the writer's own errors are the plain compile's)
+  if (wlen == rlen && std::memcmp(wtext, rtext, wlen) == 0) return plain;
+  const AvroType& wtop = *plain->avro;
+
+  auto cs = std::make_unique<CompiledSchema>();
+  cs->json.assign(wtext, wlen);
+  cs->reader_json.assign(rtext, rlen);
+  Value rj;
+  try {
+    rj = json::parse(rtext, rlen);
+    Parser p;
+    cs->avro = p.parse(rj, "");
+  } catch (const std::runtime_error& e) {
+    throw SchemaError(std::string("reader schema: ") + e.what());
+  }
+  AvroType& rtop = *cs->avro;
+  if (rtop.kind != AV_RECORD) throw SchemaError("reader schema: the top-level schema must be a record");
+  std::string why;
+  if (!supported_inner(rtop, why)) throw SchemaError("reader schema: outside the GPU direct-decode path: " + why);
+  if (rtop.name != wtop.name)
+    throw SchemaError("reader schema: record '" + rtop.name + "': the writer's record is named '" + wtop.name + "'");
+  if (rtop.fields.empty()) throw SchemaError("reader schema: record '" + rtop.name + "': no fields");
+  const Value* rfields = rj.get("fields");
+
+  // reader field <-> writer field, by name only
+  std::vector<int> keep_at(wtop.fields.size(), -1);       // writer field -> its reader field, -1 = dropped
+  std::vector<std::vector<uint8_t>> defaults(rtop.fields.size());
+  std::vector<char> defaulted(rtop.fields.size(), 0);
+  for (size_t ri = 0; ri < rtop.fields.size(); ri++) {
+    AvroField& rf = rtop.fields[ri];
+    size_t wi = 0;
+    while (wi < wtop.fields.size() && wtop.fields[wi].name != rf.name) wi++;
+    if (wi < wtop.fields.size()) {
+      const std::string m = resolve_match(*wtop.fields[wi].type, *rf.type, rf.name, true);
+      if (!m.empty()) throw SchemaError(m);
+      keep_at[wi] = (int)ri;
+      continue;
+    }
+    const Value* fj = rfields && ri < rfields->arr.size() ? &rfields->arr[ri] : nullptr;
+    const Value* dj = fj ? fj->get("default") : nullptr;
+    if (!dj) resolve_fail(rf.name, "the writer has no such field and the reader gives no default");
+    defaults[ri] = encode_default(*rf.type, *dj, rf.name);
+    defaulted[ri] = 1;
+  }
+
+  cs->projected = true;
+  cs->resolved = true;
+  cs->arrow.format = "+s";
+  cs->arrow.name = "";
+  cs->arrow.nullable = false;
+  for (auto& f : rtop.fields) {
+    cs->columns.push_back(f.name);
+    auto props = external_props(*f.type);
+    cs->arrow.children.push_back(to_field(*f.type, &f.name, false, &props));
+  }
+
+  // the writer's fields in wire order -- kept ones built as the READER declares them, the others walked and not built --
+  // then the defaulted fields, which consume no bytes
+  Builder b{*cs};
+  Builder::Ctx cx{0, false, 0, 0, 0};
+  const int id = b.new_node(NK_RECORD);
+  Builder::Ctx cc = cx;
+  cc.nest++;
+  std::vector<int> kids(rtop.fields.size(), -1);
+  for (size_t wi = 0; wi < wtop.fields.size(); wi++) {
+    if (keep_at[wi] >= 0) kids[(size_t)keep_at[wi]] = b.build(*rtop.fields[(size_t)keep_at[wi]].type, false, false, cc);
+    else b.drop(*wtop.fields[wi].type, cc);
+  }
+  for (size_t ri = 0; ri < rtop.fields.size(); ri++)
+    if (defaulted[ri]) kids[ri] = b.build_const(*rtop.fields[ri].type, defaults[ri], cc);
+  cs->nodes[(size_t)id].children = kids;
+  finish_program(*cs, b, wtop);
   return cs;
 }
 
@@ -823,4 +1115,10 @@ std::unique_ptr<CompiledSchema> compile_schema_projected(const char* text, size_
   return compile_impl(text, len, &columns);
 }
 
+}  // namespace rh
+
+namespace rh {
+std::unique_ptr<CompiledSchema> compile_schema_resolved(const char* writer, size_t wlen, const char* reader, size_t rlen) {
+  return resolve_impl(writer, wlen, reader, rlen);
+}
 }  // namespace rh

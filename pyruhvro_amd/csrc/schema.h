@@ -53,6 +53,7 @@ struct AvroType {
   std::string logical;                   // AV_OTHER_LOGICAL: its name (for messages)
   int64_t size = 0;                      // fixed: bytes | decimal / uuid on a fixed base: its size (-1: bytes / string base)
   int precision = 0, scale = 0;          // decimal
+  int wire_kind = -1;                    // resolved schemas: the writer's AvroKind of a promoted leaf (int / long / float), else -1
   std::string fullname() const { return ns.empty() ? name : ns + "." + name; }
 };
 
@@ -118,6 +119,12 @@ struct CompiledSchema {
   // hundred bytes of dropped strings per record), so the call keeps its size pass -- it classifies the tiles and hands
   // those past the window to the ranged kernels (LF_NEED_RANGED) -- although nothing has to be sized
   bool size_always = false;
+  // Reader schema (compile_schema_resolved): `json` is the WRITER's text and `prog` walks the writer's fields -- those the reader
+  // lacks carry F_DROP, promoted leaves read the writer's kind and store the reader's, reader fields the writer lacks are F_CONST
+  // ops over defaults encoded into `sym_data` (walk_resolve.h) -- while nodes, bufs, counters, row domains and `arrow` describe
+  // the READER's columns, in the reader's order.  Sets `projected` too: the engine runs the projected kernel entries, decode only.
+  bool resolved = false;
+  std::string reader_json;
 };
 
 // Throws SchemaError.  `json` need not be NUL-terminated.
@@ -126,5 +133,9 @@ std::unique_ptr<CompiledSchema> compile_schema(const char* json, size_t len);
 // order: the batch has them in that order).  Throws SchemaError naming the offender for an empty list, a duplicate, an
 // unknown name or a dotted path.
 std::unique_ptr<CompiledSchema> compile_schema_projected(const char* json, size_t len, const std::vector<std::string>& columns);
+// Records written with schema `writer`, decoded into schema `reader` (Avro 1.11 "Schema Resolution", restricted: DESIGN.md 13).
+// Throws SchemaError; every message of the resolver starts with "reader schema: " and names the field path.  A resolution that
+// changes nothing returns the plain compile of the writer.
+std::unique_ptr<CompiledSchema> compile_schema_resolved(const char* writer, size_t wlen, const char* reader, size_t rlen);
 
 }  // namespace rh

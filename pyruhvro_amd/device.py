@@ -306,13 +306,15 @@ def _pack(records) -> tuple:
 
 
 def deserialize_to_device(records, schema: str, num_chunks: int, device: int = -1, stream: int = 0, kernel: int = 0, *, columns=None,
-                          on_error: str = "raise", max_errors: int = 1024) -> DeviceDecode:
+                          on_error: str = "raise", max_errors: int = 1024, reader_schema=None) -> DeviceDecode:
     """Extension.  Decode like ``deserialize_array_threaded(records, schema, num_chunks)`` but leave the Arrow
     buffers in HBM.  ``records``: a list of ``bytes``, a pyarrow ``BinaryArray`` / ``LargeBinaryArray`` (packed on the host and
     uploaded once), or a pair ``(data, offsets)`` of device arrays that already hold the packed payload and its n + 1 uint64
     offsets (anything with ``data_ptr()`` -- torch tensors -- or raw integer addresses; ``data`` 16-byte aligned with 64 readable
     bytes of slack).  ``stream``: the HIP stream to launch on (e.g. ``torch.cuda.current_stream().cuda_stream``).
     ``columns``: only these top-level fields, in this order (the other columns get no device buffers at all).
+    ``reader_schema``: ``schema`` is the writer's, the device batches are in this Avro schema (see ``deserialize_array``);
+    ``columns`` then names reader fields.  Not with ``on_error="placeholder"``.
     Errors are the reference's: ``ValueError`` with its message for a malformed datum or an unsupported schema.
     ``on_error="placeholder"``: a malformed record does not abort the call; it is replaced by ``placeholder_datum(schema)`` and
     listed in the result's ``.errors`` (``[RecordError(index, message)]``, ascending; at most ``max_errors``, beyond which the
@@ -323,7 +325,9 @@ def deserialize_to_device(records, schema: str, num_chunks: int, device: int = -
         raise TypeError("argument 'num_chunks': expected int")
     if num_chunks < 0:
         raise OverflowError("can't convert negative int to unsigned")
-    s = cabi.Schema.get(schema, columns)
+    if on_error == "placeholder":
+        cabi.refuse_reader_schema(reader_schema, "a tolerant decode")
+    s = cabi.Schema.get(schema, columns, reader_schema)
     keep = []
     if isinstance(records, tuple) and len(records) == 2 and not isinstance(records[0], (bytes, bytearray)):
         d_data, d_off = records
@@ -349,7 +353,8 @@ def deserialize_to_device(records, schema: str, num_chunks: int, device: int = -
             r = cabi.decode_device_tolerant(p_data, p_off, data_len, n, schema, num_chunks, device=device, stream=stream, kernel=kernel,
                                             columns=columns, max_errors=check_max_errors(max_errors))
         else:
-            r = cabi.decode_device(p_data, p_off, data_len, n, schema, num_chunks, device=device, stream=stream, kernel=kernel, columns=columns)
+            r = cabi.decode_device(p_data, p_off, data_len, n, schema, num_chunks, device=device, stream=stream, kernel=kernel, columns=columns,
+                                   reader_schema=reader_schema)
     finally:
         for k in keep:
             if isinstance(k, _DevMem):

@@ -13,9 +13,12 @@ from typing import Iterable, List, Tuple
 
 
 def _one(item) -> Tuple[bool, str]:
-    """`item`: a schema string, or (schema string, columns) for the kernels of a projection."""
+    """`item`: a schema string, (schema string, columns) for the kernels of a projection, or ("resolve", writer schema
+    string, reader schema string) for those of a resolution."""
     from pyruhvro_amd import cabi
     try:
+        if isinstance(item, tuple) and len(item) == 3 and item[0] == "resolve":
+            return cabi.prebuild(item[1], reader_schema=item[2]), ""
         if isinstance(item, tuple):
             return cabi.prebuild(item[0], columns=item[1]), ""
         return cabi.prebuild(item), ""

@@ -9,7 +9,7 @@ import sys
 from typing import List
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-for _p in (ROOT, os.path.join(ROOT, "tests")):
+for _p in (ROOT, os.path.join(ROOT, "tests"), os.path.join(ROOT, "scripts")):
     if _p not in sys.path:
         sys.path.insert(0, _p)
 
@@ -76,6 +76,14 @@ def known_projections() -> list:
     return list(dict.fromkeys(out))
 
 
+def known_resolutions() -> list:
+    """(writer, reader) pairs whose resolved kernels (`reader_schema=`: rh_schema_resolve) the GPU tests and
+    scripts/resolution_bench.py decode with: prebuilt by this script next to the projections."""
+    import resolve_cases
+    import resolution_bench
+    return list(dict.fromkeys(resolve_cases.resolution_cases() + [(resolution_bench.WRITER, r) for r in resolution_bench.readers().values()]))
+
+
 def single_pass_schemas() -> List[str]:
     """The schemas whose single-pass kernel (rh_spec_fused) a bench line or a test runs: the only ones build() compiles it for --
     it is the most expensive of a schema's five kernels and opt-in; every other schema gets it on first request."""
@@ -96,6 +104,7 @@ if __name__ == "__main__":
     os.environ["RUHVRO_HIP_PREBUILD_FUSED"] = "0"
     errs += prebuild_many(rest, verbose=True)
     errs += prebuild_many(known_projections(), verbose=True)      # (without their single-pass kernel: compiled on first request)
+    errs += prebuild_many([("resolve", w, r) for w, r in known_resolutions()], verbose=True)
     if not errs:
         from pyruhvro_amd.prebuild import mark_warm
         mark_warm(known_schemas())
