@@ -57,6 +57,9 @@ def known_schemas() -> List[str]:
         out.append(test_n4_types.DUR_SCHEMA)
         import test_named_refs                    # named-type references (resolved by the front-end)
         out.append(test_named_refs.WITH_REFS)
+        import damage                             # tolerant-decode fuzz (its other schemas are listed above)
+        out.append(damage.LONG_PLACEHOLDER_SCHEMA)
+        out.append(damage.UNION_NO_NULL_SCHEMA)
         g = json.load(open(os.path.join(root, "tests", "golden", "reference_vectors.json")))
         out += [json.dumps(s) for s in g["schemas"].values()]
     except ImportError:
@@ -73,6 +76,7 @@ def known_projections() -> list:
     import test_projection
     out = [(s, tuple(c)) for s, c in test_projection.projection_cases()]
     out += [(SCHEMAS["full"], c) for c in (("created_at", "age"), ("name", "created_at", "class"), ("emails", "phone_numbers"))]
+    out.append((SCHEMAS["full"], ("created_at", "name")))      # the tolerant tests' projection
     return list(dict.fromkeys(out))
 
 
