@@ -259,6 +259,40 @@ int rh_schema_prebuild(const rh_schema* s, int* cached, char** err);
  * at full speed calls rh_schema_prebuild at start-up instead; this is for the ones that would rather start serving. */
 int rh_schema_kernels_ready(const rh_schema* s, int encode, long timeout_ms, char** err);
 
+/* The LEAN pair (added without a change of RH_ABI_VERSION: callers look these symbols up with dlsym).  rh_spec_size and
+ * rh_spec_emit once more, compiled from the default source behind `#define RH_V_LEN16 1` and `#define RH_V_INT28 1` (walk.h):
+ * lengths and block counts are read in the 2-byte form and ints in the 4-byte form.  A record that leaves those forms is
+ * re-walked carefully and its tile flagged, so the pair is correct on any input; it is faster on batches of short varints
+ * and slower on others, and the engine chooses per (schema, device): a qualifying call (AUTO or SPECIALIZED kernels, two-pass,
+ * no ranged pair in the call, at least RUHVRO_HIP_LEAN_MIN_RECORDS records -- default 1,000,000, 0 = never) probes a sample
+ * of its own tiles with the lean size kernel; a clean probe moves the schema to the lean pair, a lean call that meets a
+ * careful tile or a re-walked wavefront moves it back for 8, 16, ... 1024 calls.  RUHVRO_HIP_LEAN=0 / 1: never / always.
+ * A schema without a size pass and a wide schema have no lean pair.  rh_schema_kernel_source, rh_schema_kernel_key and
+ * rh_schema_kernels_ready keep describing the default (wide) kernels, which the measurement stamps belong to.
+ *   rh_schema_lean_kernel_source / _key   the lean source (malloc'd) and its kernel-cache key; NULL = no lean pair
+ *   rh_schema_lean_ready                  like rh_schema_kernels_ready for the lean pair; -2 = the schema has none
+ *   rh_schema_lean_state                  -1 no lean pair, 0 undecided, 1 lean, 2 wide -- of this schema on `device`
+ *   rh_lean_counters                      fills out[0..n) with the RH_LEAN_* values below, returns RH_LEAN_COUNT */
+char* rh_schema_lean_kernel_source(const rh_schema* s);
+char* rh_schema_lean_kernel_key(const rh_schema* s);
+int rh_schema_lean_ready(const rh_schema* s, long timeout_ms, char** err);
+int rh_schema_lean_state(const rh_schema* s, int device);
+enum {
+  RH_LEAN_CALLS = 0,            /* decode calls that launched the lean pair                                                  */
+  RH_LEAN_PROBES = 1,           /* probes settled (the lean size kernel over a sample of a call's tiles)                       */
+  RH_LEAN_PROBES_CLEAN = 2,     /* ... without a careful tile, a re-walked wavefront or an error: the schema went lean         */
+  RH_LEAN_PROBES_DIRTY = 3,     /* ... with one: the schema stays wide, the next probe comes 64 qualifying calls later         */
+  RH_LEAN_FALLBACKS = 4,        /* lean calls whose own tile statistics moved the schema back to the wide pair                */
+  RH_LEAN_RERUNS = 5,           /* lean calls repeated on another form by the settlement of an RH_ASYNC result                */
+  RH_LEAN_NEED_RANGED = 6,      /* lean calls refused for a tile past the LDS window (repeated on the generic kernels)         */
+  RH_LEAN_NEED_WIDE_INDEX = 7,  /* lean calls whose layout needs 64-bit indexing (repeated on the generic kernels)             */
+  RH_LEAN_TWO_PASS_REPEATS = 8, /* two-pass repeats of a failed single-pass call that launched the lean pair                  */
+  RH_LEAN_CAPACITY_TAILS = 9,   /* lean calls whose reserved arena was too small: tail re-run with the lean emit kernel        */
+  RH_LEAN_ASYNC_SETTLED = 10,   /* lean calls made with RH_ASYNC and settled later                                             */
+  RH_LEAN_COUNT = 11
+};
+uint32_t rh_lean_counters(uint64_t* out, uint32_t n);
+
 /* Arrow -> Avro, the other direction.  Replaces ruhvro::serialize::serialize_record_batch
  * (ruhvro/src/serialize.rs:38-67) + fast_encode::serialize_chunk (ruhvro/src/fast_encode.rs:27-53): `batch` is
  * the record batch as a struct array (Arrow C Data Interface, any offsets / slices), columns are matched to the

@@ -315,6 +315,68 @@ def kernel_key(schema_json: str, encode: bool = False, columns=None, reader_sche
         L.rh_free_string(p)
 
 
+# The lean pair (include/ruhvro_hip.h): symbols added without a change of the ABI version, so they are looked up by name
+# when first asked for -- a library built before them answers "no lean pair".
+LEAN_COUNTERS = ("lean_calls", "probes", "probes_clean", "probes_dirty", "fallbacks", "reruns", "need_ranged", "need_wide_index",
+                 "two_pass_repeats", "capacity_tails", "async_settled")
+LEAN_NONE, LEAN_UNDECIDED, LEAN_LEAN, LEAN_WIDE = -1, 0, 1, 2
+
+
+def _lean_sym(name: str, restype, argtypes):
+    f = getattr(lib(), name, None)          # (ctypes: dlsym)
+    if f is not None:
+        f.restype, f.argtypes = restype, argtypes
+    return f
+
+
+def _lean_string(name: str, schema_json: str, columns=None, reader_schema=None):
+    f = _lean_sym(name, C.c_void_p, [C.c_void_p])
+    p = f(Schema.get(schema_json, columns, reader_schema).handle) if f else None
+    if not p:
+        return None
+    try:
+        return C.string_at(p).decode()
+    finally:
+        lib().rh_free_string(p)
+
+
+def lean_kernel_source(schema_json: str, columns=None, reader_schema=None):
+    """HIP source of the schema's lean pair (rh_schema_lean_kernel_source), or None when the schema has none."""
+    return _lean_string("rh_schema_lean_kernel_source", schema_json, columns, reader_schema)
+
+
+def lean_kernel_key(schema_json: str, columns=None, reader_schema=None):
+    """Kernel-cache key of the lean source (rh_schema_lean_kernel_key), or None."""
+    return _lean_string("rh_schema_lean_kernel_key", schema_json, columns, reader_schema)
+
+
+def lean_state(schema_json: str, device: int = 0, columns=None, reader_schema=None) -> int:
+    """rh_schema_lean_state: LEAN_NONE / LEAN_UNDECIDED / LEAN_LEAN / LEAN_WIDE of this schema on `device`."""
+    f = _lean_sym("rh_schema_lean_state", C.c_int, [C.c_void_p, C.c_int])
+    return int(f(Schema.get(schema_json, columns, reader_schema).handle, device)) if f else LEAN_NONE
+
+
+def lean_ready(schema_json: str, timeout_ms: int = 0) -> bool:
+    """rh_schema_lean_ready: True when the lean pair's code objects are there."""
+    f = _lean_sym("rh_schema_lean_ready", C.c_int, [C.c_void_p, C.c_long, C.POINTER(C.c_char_p)])
+    if f is None:
+        return False
+    err = C.c_char_p()
+    rc = f(Schema.get(schema_json).handle, int(timeout_ms), C.byref(err))
+    if rc == -1:
+        _raise(RH_ERR_RUNTIME, err)
+    return rc == 1
+
+
+def lean_counters() -> dict:
+    """rh_lean_counters by name: the roads of the lean pair (none of them moves rh_engine_counters)."""
+    f = _lean_sym("rh_lean_counters", C.c_uint32, [C.POINTER(C.c_uint64), C.c_uint32])
+    buf = (C.c_uint64 * len(LEAN_COUNTERS))()
+    if f is not None:
+        assert f(buf, len(LEAN_COUNTERS)) == len(LEAN_COUNTERS)
+    return {name: int(buf[i]) for i, name in enumerate(LEAN_COUNTERS)}
+
+
 def encode_kernel_source(schema_json: str) -> str:
     """HIP source of the schema-specialised Arrow -> Avro kernels (rh_schema_encode_kernel_source)."""
     L = lib()

@@ -83,6 +83,11 @@ uint32_t rh_engine_counters(uint64_t* out, uint32_t n) {
   return RH_CTR_COUNT;
 }
 
+uint32_t rh_lean_counters(uint64_t* out, uint32_t n) {
+  for (uint32_t i = 0; i < n && i < (uint32_t)LC_COUNT; i++) out[i] = g_lean_counters[i].load(std::memory_order_relaxed);
+  return LC_COUNT;
+}
+
 int rh_device_count(void) {
   int n = 0;
   if (hipGetDeviceCount(&n) != hipSuccess) return 0;
@@ -280,6 +285,51 @@ char* rh_schema_kernel_key(const rh_schema* s, int encode) {
   }
 }
 
+char* rh_schema_lean_kernel_source(const rh_schema* s) {
+  if (!s) return nullptr;
+  try {
+    const std::string src = rh::generate_lean_source(*s->cs);
+    return src.empty() ? nullptr : dup_msg(src);
+  } catch (...) {
+    return nullptr;
+  }
+}
+
+char* rh_schema_lean_kernel_key(const rh_schema* s) {
+  if (!s) return nullptr;
+  try {
+    const std::string src = rh::generate_lean_source(*s->cs);
+    return src.empty() ? nullptr : dup_msg(rh::kernel_cache_key(src, false));
+  } catch (...) {
+    return nullptr;
+  }
+}
+
+int rh_schema_lean_ready(const rh_schema* s, long timeout_ms, char** err) {
+  if (!s) return -1;
+  try {
+    if (!rh::schema_has_lean(*s->cs)) return -2;
+    rh::KernelImage im[rh::KP_COUNT];
+    rh::kernel_images(s->images, *s->cs, rh::kLeanParts, rh::CP_CACHED_ONLY, im);      // (a first look at the disk cache; starts nothing)
+    std::string why;
+    const int rc = rh::kernel_images_wait(s->images, rh::kLeanParts, timeout_ms, &why);
+    if (rc < 0 && err) *err = dup_msg(why);
+    return rc;
+  } catch (const std::exception& e) {
+    if (err) *err = dup_msg(e.what());
+    return -1;
+  }
+}
+
+int rh_schema_lean_state(const rh_schema* cs_, int device) {
+  rh_schema* s = const_cast<rh_schema*>(cs_);
+  if (!s) return -1;
+  if (!rh::schema_has_lean(*s->cs)) return -1;
+  std::lock_guard<std::mutex> g(s->mu);
+  auto it = s->spec.find(device);
+  return (it == s->spec.end() || !it->second) ? 0 : it->second->lean_state;
+}
+
 char* rh_schema_encode_kernel_source(const rh_schema* s) {
   if (!s || !s->cs->encode_unsupported.empty() || s->cs->projected) return nullptr;
   try {
@@ -299,8 +349,13 @@ int rh_schema_prebuild(const rh_schema* s, int* cached, char** err) {
     //  a schema first meets such tiles otherwise)
     const bool fused = env_long("RUHVRO_HIP_PREBUILD_FUSED", 1, 0, 1) != 0;
     const bool ranged = env_long("RUHVRO_HIP_PREBUILD_RANGED", 1, 0, 1) != 0;
+    // (RUHVRO_HIP_PREBUILD_LEAN=1: also the lean pair -- compiled in the background behind the schema's first qualifying call
+    //  otherwise.  Opt-in, unlike the two above: the set of code objects a plain prebuild leaves in the cache is pinned by
+    //  tests/test_specialize.py; pyruhvro_amd/prebuild.py turns it on for the benchmark schemas.)
+    const bool lean = env_long("RUHVRO_HIP_PREBUILD_LEAN", 0, 0, 1) != 0;
     const unsigned parts = (rh::kDecodeParts & ~(fused ? 0u : (1u << rh::KP_FUSED)) & ~(ranged ? 0u : ((1u << rh::KP_SIZE_R) | (1u << rh::KP_EMIT_R)))) |
-                           ((s->cs->encode_unsupported.empty() && !s->cs->wide && !s->cs->projected) ? rh::kEncodeParts : 0u);      // (a wide schema's Arrow -> Avro pair is compiled by its first rh_encode: the encode generator unrolls every column)
+                           ((s->cs->encode_unsupported.empty() && !s->cs->wide && !s->cs->projected) ? rh::kEncodeParts : 0u) |
+                           (lean ? rh::kLeanParts : 0u);      // (a wide schema's Arrow -> Avro pair is compiled by its first rh_encode: the encode generator unrolls every column)
     rh::KernelImage im[rh::KP_COUNT];
     const unsigned started = rh::kernel_images(s->images, *s->cs, parts, rh::CP_BLOCKING, im);
     for (int p = 0; p < rh::KP_COUNT; p++) {

@@ -32,6 +32,15 @@ struct rh_decode_call {
   const DeviceProgram* dp = nullptr;
   const SpecKernel* sk = nullptr;
   hipFunction_t size_r = nullptr, emit_r = nullptr;     // the ranged pair, when this call launches it (tiles past the LDS window)
+  // The pair the two-pass form launches: the schema's default (wide) rh_spec_size / rh_spec_emit, or its lean pair (lean_select)
+  hipFunction_t size_f = nullptr, emit_f = nullptr;
+  hipFunction_t lean_size = nullptr, lean_emit = nullptr;      // the lean pair, loaded, when this call qualifies for it
+  bool lean = false;            // ... and launches it
+  // the probe (launch_probe): the lean size kernel over a sample of this call's tiles, on a workspace and control block of its own
+  bool probing = false;
+  uint32_t probe_token = 0;
+  Lease probe_ws, probe_host;
+  std::unique_ptr<CtrlLease> probe_ctrl;
   uint64_t narrow_rows = 0, tile = 0, bpc64 = 0, payload = 0;
   uint32_t nblocks = 0;
   uint64_t o_null = 0, o_tot = 48, ctrl_bytes = 0;
@@ -126,7 +135,10 @@ struct rh_decode_call {
     if (sk)
       for (int d = 1; d < cs.ndom; d++)
         for (uint32_t c = 0; c < k; c++)
-          if (totals[(size_t)(d - 1) * k + c] >= narrow_rows) throw NeedWideIndex();
+          if (totals[(size_t)(d - 1) * k + c] >= narrow_rows) {
+            if (lean) lean_count(LC_NEED_WIDE_INDEX);
+            throw NeedWideIndex();
+          }
     r.fill_tables();
     exact = r.output_bytes;
   }
@@ -136,7 +148,7 @@ struct rh_decode_call {
         rh_launch_init(P.bufptr, d_sizes, dp->desc, (uint32_t)nbuf, k, P.first_bad, stream)) throw HipError("k_init launch failed");
     if (n > 0) {
       emit_lds = lds_bytes;
-      if (sk ? launch_module(sk->emit_fn, P, nblocks, (uint32_t)tile, emit_lds, stream, ev.at(3), P.ranged ? nullptr : ev.at(4))
+      if (sk ? launch_module(emit_f, P, nblocks, (uint32_t)tile, emit_lds, stream, ev.at(3), P.ranged ? nullptr : ev.at(4))
              : (cs.projected ? rh_launch_emit_drop : rh_launch_emit)(&P, emit_lds, stream, ev.at(3), ev.at(4)))
         throw HipError("k_emit launch failed");
       if (P.ranged && launch_module(emit_r, P, nblocks + (P.worklist ? rh::kBigFront : 0u), (uint32_t)tile, emit_lds, stream, nullptr, ev.at(4))) throw HipError("k_emit (ranged) launch failed");
@@ -167,6 +179,147 @@ struct rh_decode_call {
     HIPCHK(hipMemcpyAsync(hctrl.ptr() + o_null, ctrl->ptr() + o_null, ctrl_bytes - o_null, hipMemcpyDeviceToHost, stream));
     HIPCHK(hipStreamSynchronize(stream));      // also keeps htab alive until the table copy is done
     check_bad(hctrl.ptr());
+  }
+
+  // ---- the lean pair (specialize.h KP_SIZE_L / KP_EMIT_L; include/ruhvro_hip.h) ----
+  // Does this two-pass call qualify, and which pair does it launch?  Qualifying: AUTO or SPECIALIZED kernels, a size pass, no
+  // ranged pair in the call, a schema that has a lean pair, n >= RUHVRO_HIP_LEAN_MIN_RECORDS (0 = never); RUHVRO_HIP_LEAN=0 / 1
+  // = never / always.  All read per call.  The lean pair is launched only by the single-submission form, whose scan launch
+  // sums the tile statistics the selection learns from (lean_learn).  A pair that is not loaded yet starts compiling in the
+  // background (RUHVRO_HIP_LEAN=1 waits for it) and the call goes ahead on the wide pair.
+  SpecKernel& sel() const { return const_cast<SpecKernel&>(*sk); }
+  void lean_select() {
+    if (!sk || !timed_size || P.ranged || sk->lean_dead || !rh::schema_has_lean(cs)) return;
+    const long force = env_long("RUHVRO_HIP_LEAN", -1, 0, 1);
+    const long min_n = env_long("RUHVRO_HIP_LEAN_MIN_RECORDS", 1000000, 0, 1l << 40);
+    if (force == 0 || min_n == 0 || n < (uint64_t)min_n) return;
+    hipFunction_t el = sk->emit_l_fn.load(std::memory_order_acquire);
+    if (!el) el = spec_kernel(s, device, force == 1 ? rh::CP_BLOCKING : rh::CP_BACKGROUND, false, false, false, true).emit_l_fn.load(std::memory_order_acquire);
+    if (!el) return;
+    lean_emit = el;
+    lean_size = sk->size_l_fn.load(std::memory_order_acquire);
+    bool use = force == 1;
+    if (!use) {
+      std::lock_guard<std::mutex> g(s->mu);
+      use = sel().lean_state == SpecKernel::LS_LEAN;
+    }
+    if (use && fused) {
+      size_f = lean_size; emit_f = lean_emit; lean = true;
+      lean_count(LC_LEAN_CALLS);
+      if (opts.flags & RH_INTERNAL_TWO_PASS) lean_count(LC_TWO_PASS_REPEATS);
+    }
+  }
+
+  // The probe of a qualifying call that runs on the wide pair while the schema is undecided, or wide with its wait used up: the
+  // lean size kernel over the first tiles of (up to 64 of) the call's chunks -- 64 tiles and more, or all the call has -- through
+  // a KParams that describes just those tiles (kernel_common.h geometry: chunk stride sz, `bpc` tiles per chunk).  It writes a
+  // workspace and a control block of its own; rh_k_tile_stats sums its tile flags and rh_k_publish hands the head over.
+  // Three small launches behind the call's own; counts nothing in rh_engine_counters.
+  void launch_probe() {
+    if (!lean_size || lean || n == 0 || env_long("RUHVRO_HIP_LEAN", -1, 0, 1) >= 0) return;
+    const uint32_t kp = std::min<uint32_t>(k, 64);
+    const uint32_t per = (uint32_t)std::min<uint64_t>(bpc64, (64 + kp - 1) / kp);
+    const uint64_t rows_lastp = kp == k ? r.rows_last : r.sz;
+    const uint32_t tiles_last = (uint32_t)std::min<uint64_t>(per, (rows_lastp + tile - 1) / tile);
+    if (per == 0 || tiles_last == 0) return;
+    const uint32_t pn = (kp - 1) * per + tiles_last;
+    {
+      std::lock_guard<std::mutex> g(s->mu);
+      SpecKernel& sl = sel();
+      if (sl.lean_state == SpecKernel::LS_LEAN || sl.lean_probing) return;
+      if (sl.lean_state == SpecKernel::LS_WIDE && sl.lean_wait > 0) { sl.lean_wait--; return; }
+      sl.lean_probing = true;
+    }
+    probing = true;          // (from here on drain() / probe_settle() give the schema's flag back)
+    const uint64_t q_bsum = align_up(sizeof(rh::ErrInfo) * (uint64_t)pn, kAlign);
+    const uint64_t q_flag = align_up(q_bsum + 4ull * std::max(K, 1) * pn, kAlign);
+    const uint64_t q_lcnt = align_up(q_flag + 4ull * pn, kAlign);
+    const uint64_t q_end = align_up(q_lcnt + 4ull * (uint64_t)((cs.KL + 1) / 2) * pn * tile, kAlign) + kAlign;
+    probe_ws = Lease(dev_pool(), q_end, device);
+    probe_host = Lease(pin_pool(), 256, device);
+    probe_ctrl.reset(new CtrlLease(ctrl_bytes, device, stream));      // all zero; zeroed again on its way back (CtrlPool)
+    void* hdev = nullptr;
+    if (hipHostGetDevicePointer(&hdev, probe_host.ptr(), 0) != hipSuccess || !hdev) {
+      (void)hipGetLastError();
+      probe_abandon();
+      return;
+    }
+    rh::KParams Q = P;
+    Q.k = kp; Q.rows_last = rows_lastp; Q.bpc = per; Q.nblocks = pn;
+    Q.ranged = 0; Q.worklist = nullptr; Q.bigmark = nullptr; Q.all_careful = 0; Q.lookback = nullptr; Q.caps = nullptr;
+    Q.first_bad = (unsigned long long*)probe_ctrl->ptr();
+    Q.nullcount = (uint32_t*)(probe_ctrl->ptr() + o_null);
+    Q.totals = (uint64_t*)(probe_ctrl->ptr() + o_tot);
+    Q.tickets = (uint32_t*)(probe_ctrl->ptr() + o_tick);
+    Q.errinfo = (rh::ErrInfo*)probe_ws.ptr();
+    Q.blocksum = (uint32_t*)(probe_ws.ptr() + q_bsum);
+    Q.blockbase = Q.blocksum;                              // (not read by the size kernel)
+    Q.tileflag = (uint32_t*)(probe_ws.ptr() + q_flag);
+    Q.lanecnt = (uint32_t*)(probe_ws.ptr() + q_lcnt);
+    Q.lanecnt32 = nullptr;
+    static std::atomic<uint32_t> next_token{0x20000001u};
+    probe_token = next_token.fetch_add(1);
+    if (probe_token == 0) probe_token = next_token.fetch_add(1);
+    *(volatile uint32_t*)(probe_host.ptr() + 48) = 0;
+    if (launch_module(lean_size, Q, pn, (uint32_t)tile, lds_bytes, stream) ||
+        rh_launch_tile_stats(probe_ctrl->ptr(), Q.tileflag, pn, stream) ||
+        rh_launch_publish(probe_ctrl->ptr(), hdev, 12, 0, 12, probe_token, null_slots, stream))
+      throw HipError("lean probe launch failed");
+  }
+
+  void probe_abandon() noexcept {      // the probe did not run (or its call is being drained): another call may probe
+    if (!probing) return;
+    probing = false;
+    std::lock_guard<std::mutex> g(s->mu);
+    sel().lean_probing = false;
+  }
+
+  // Behind the call's own wait: the probe's head (first_bad, layout flag, tile statistics) is in probe_host behind its token.
+  // No malformed record, no refusal, no careful tile and no re-walked wavefront in the sample: the schema goes lean.  Anything
+  // else: wide, and the next probe comes 64 qualifying calls later.
+  void probe_settle() {
+    if (!probing) return;
+    volatile uint32_t* flag = (volatile uint32_t*)(probe_host.ptr() + 48);
+    bool got = true;
+    for (uint32_t spins = 0; __atomic_load_n(flag, __ATOMIC_ACQUIRE) != probe_token;) {
+      if ((++spins & 0xFFFFu) == 0) {
+        const hipError_t q = hipStreamQuery(stream);
+        if (q == hipErrorNotReady) continue;
+        got = __atomic_load_n(flag, __ATOMIC_ACQUIRE) == probe_token;      // the stream is done (or failed): the token is there or never will be
+        break;
+      }
+    }
+    const uint32_t* h = (const uint32_t*)probe_host.ptr();
+    const bool clean = got && h[0] == 0 && h[1] == 0 && h[2] == 0 && h[8] == 0 && h[9] == 0 && h[10] == 0;
+    lean_count(LC_PROBES);
+    lean_count(clean ? LC_PROBES_CLEAN : LC_PROBES_DIRTY);
+    {
+      std::lock_guard<std::mutex> g(s->mu);
+      SpecKernel& sl = sel();
+      sl.lean_probing = false;
+      if (clean) sl.lean_state = SpecKernel::LS_LEAN;
+      else { sl.lean_state = SpecKernel::LS_WIDE; sl.lean_wait = 64; }
+    }
+    probing = false;
+    if (got) { probe_ws.release(); probe_host.release(); probe_ctrl.reset(); }      // (else: kept until the call is drained)
+  }
+
+  // A lean call's own tile statistics decide the schema's future: a careful tile or a re-walked wavefront (or a refusal) moves
+  // it back to the wide pair for 8, 16, ... 1024 qualifying calls (as single_backoff does); a clean lean call clears the backoff.
+  void lean_learn(bool dirty) {
+    if (!lean) return;
+    std::lock_guard<std::mutex> g(s->mu);
+    SpecKernel& sl = sel();
+    if (dirty) {
+      if (sl.lean_state != SpecKernel::LS_WIDE) {
+        sl.lean_backoff = std::min<uint32_t>(1024, std::max<uint32_t>(8, sl.lean_backoff * 2));
+        sl.lean_wait = sl.lean_backoff;
+        sl.lean_state = SpecKernel::LS_WIDE;
+        lean_count(LC_FALLBACKS);
+      }
+    } else if (sl.lean_state == SpecKernel::LS_LEAN) {
+      sl.lean_backoff = 0;
+    }
   }
 
   // The single-pass form (spec_body.h spec_fused): k_layout over per-column CAPACITIES from the schema's history, then ONE
@@ -473,11 +626,14 @@ struct rh_decode_call {
     if (start_after) HIPCHK(hipStreamWaitEvent(stream, start_after, 0));
     if (try_single(two_sync, ratio_hook)) return;
     timed_size = n > 0 && size_pass;
+    size_f = sk ? sk->size_fn : nullptr;
+    emit_f = sk ? sk->emit_fn : nullptr;
+    lean_select();
     if (timed_size) {
       if (P.worklist) HIPCHK(hipMemsetAsync(P.worklist, 0, 8ull + 8ull * nblocks, stream));      // the list's length, every tile's mark
 
       // (with the ranged pair: the size kernel's start and the ranged size kernel's stop bracket the pass)
-      if (sk ? launch_module(sk->size_fn, P, nblocks, (uint32_t)tile, lds_bytes, stream, ev.at(0), P.ranged ? nullptr : ev.at(1))
+      if (sk ? launch_module(size_f, P, nblocks, (uint32_t)tile, lds_bytes, stream, ev.at(0), P.ranged ? nullptr : ev.at(1))
              : (cs.projected ? rh_launch_size_drop : rh_launch_size)(&P, lds_bytes, stream, ev.at(0), ev.at(1)))
         throw HipError("k_size launch failed");
       if (P.ranged && launch_module(size_r, P, nblocks + (P.worklist ? rh::kBigFront : 0u), (uint32_t)tile, lds_bytes, stream, nullptr, ev.at(1))) throw HipError("k_size (ranged) launch failed");
@@ -538,6 +694,7 @@ struct rh_decode_call {
       }
       hp.mark("d2h_enqueue");
     }
+    launch_probe();
   }
 
   void finish() {
@@ -568,6 +725,7 @@ struct rh_decode_call {
         HIPCHK(hipStreamSynchronize(stream));
       }
       hp.mark("sync");
+      probe_settle();
       const uint32_t lflag = *(const uint32_t*)(hctrl.ptr() + 8);
       // a tile past the LDS window and no ranged pair in this call: nothing was emitted.  The refused attempt counts nothing
       // (its tiles past the window never wrote their flag words, and the device summed none): the repeat of the call does.
@@ -577,9 +735,12 @@ struct rh_decode_call {
         ctrl->b.clean = published;
         s->ranged_calls.store(kRangedKeep, std::memory_order_relaxed);
         r.arena.release();
+        if (lean) { lean_count(LC_NEED_RANGED); lean_learn(true); }
         throw NeedRanged();
       }
       check_bad(hctrl.ptr());
+      // (a lean call reads its statistics whichever way the head came back: the scan launch summed them into the control block)
+      if (lean && !single) { const uint32_t* stw = (const uint32_t*)(hctrl.ptr() + 32); lean_learn(stw[0] != 0 || stw[2] != 0); }
       if (published && timed_size && !single) {      // the tile statistics the scan launch summed (include/ruhvro_hip.h RH_CTR_*_TILES)
         const uint32_t* stw = (const uint32_t*)(hctrl.ptr() + 32);
         count(RH_CTR_TILES, nblocks);
@@ -609,6 +770,7 @@ struct rh_decode_call {
         { std::lock_guard<std::mutex> g(s->mu); s->single_backoff = 0; }
       } else if (lflag & rh::LF_CAPACITY) {
         count(RH_CTR_CAPACITY_RETRIES);
+        if (lean) lean_count(LC_CAPACITY_TAILS);
         r.arena.release();
         exact_tail();                              // (throws the offset-overflow / wide-index cases itself)
       } else if (lflag || want_stats) {
@@ -626,6 +788,7 @@ struct rh_decode_call {
       if (timed_size) {
         HIPCHK(hipMemcpyAsync(hctrl.ptr(), ctrl->ptr(), ctrl_bytes, hipMemcpyDeviceToHost, stream));
         HIPCHK(hipStreamSynchronize(stream));
+        probe_settle();
         if (*(const uint32_t*)(hctrl.ptr() + 8) & rh::LF_NEED_RANGED) {      // (ahead of the error check, as above)
           ctrl->b.clean = false;
           s->ranged_calls.store(kRangedKeep, std::memory_order_relaxed);
@@ -694,11 +857,13 @@ struct rh_decode_call {
     }
     // the call's scratch goes back to the pools now (the control block is zeroed on its stream, CtrlPool)
     ws.release(); dtab.release(); hctrl.release(); prof_buf.release(); lookback.release(); hcaps.release(); ctrl.reset();
+    probe_settle();      // (a path that waited for the stream some other way: by now the probe is done too)
   }
 
   // a call that failed (or is abandoned) must not hand its blocks back while the GPU may still be using them
   void drain() noexcept {
     if (stream || device >= 0) { (void)hipSetDevice(device); (void)hipStreamSynchronize(stream); }
+    probe_abandon();
   }
 };
 
@@ -733,6 +898,7 @@ rh_device_result* decode_device_impl1(rh_schema* s, const uint8_t* d_data, const
   try {
     call->enqueue();
     if (async && call->fused) {            // everything is on the stream: settle later (rh_device_result_wait)
+      if (call->lean) lean_count(LC_ASYNC_SETTLED);
       res->pending = std::move(call);
       return res.release();
     }
@@ -884,6 +1050,7 @@ void settle(rh_device_result* r) {
   // the call again, synchronously, on another form: the two-pass form (a single-pass call that outgrew a capacity) or the
   // generic kernels (a child row domain beyond 32-bit indexing -- which the two-pass repeat may itself run into)
   auto rerun = [&](int add_flags, bool generic) {
+    if (call->lean) lean_count(LC_RERUNS);
     call->drain();
     rh_opts o = call->opts;
     o.flags = generic ? ((o.flags & ~(3 | RH_ASYNC)) | RH_KERNEL_GENERIC) : ((o.flags & ~RH_ASYNC) | add_flags);

@@ -347,12 +347,23 @@ struct DeviceProgram {
 };
 
 struct SpecKernel {      // schema-specialised kernels loaded on one device (each kernel is its own code object, kernel_jobs.h)
-  hipModule_t mod[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+  hipModule_t mod[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
   hipFunction_t size_fn = nullptr, emit_fn = nullptr;
   // the ranged pair (tiles past the LDS window, spec_body.h ranged_tile): compiled and loaded when the schema first meets such
   // tiles; both or neither (emit_r_fn is stored last)
   std::atomic<hipFunction_t> size_r_fn{nullptr}, emit_r_fn{nullptr};
   std::atomic<bool> ranged_dead{false};
+  // the lean pair (specialize.h KP_SIZE_L / KP_EMIT_L: the same two kernels with walk.h's narrow single-read forms), loaded when
+  // a call of the schema first qualifies for it; both or neither (emit_l_fn is stored last)
+  std::atomic<hipFunction_t> size_l_fn{nullptr}, emit_l_fn{nullptr};
+  std::atomic<bool> lean_dead{false};   // no such pair for this schema (no size pass, or wide), or its compile failed
+  // Which pair the schema's qualifying calls on this device launch (engine_device_call.cpp lean_select / lean_learn), under
+  // rh_schema::mu.  Correctness never depends on it: the lean pair re-walks and flags what leaves its forms.
+  enum : int { LS_UNDECIDED = 0, LS_LEAN = 1, LS_WIDE = 2 };
+  int lean_state = LS_UNDECIDED;
+  uint32_t lean_wait = 0;               // LS_WIDE: qualifying calls until the next probe
+  uint32_t lean_backoff = 0;            // calls LS_WIDE lasts after a lean call met a careful tile (8, 16, ... 1024; a clean lean call clears it)
+  bool lean_probing = false;            // a probe is on a stream: one at a time
   // the single-pass form (decode kernels only): compiled and loaded when a call first asks for it, so it is written while
   // other calls of the schema read it
   std::atomic<hipFunction_t> fused_fn{nullptr};
@@ -396,7 +407,13 @@ namespace rhe {
 const DeviceProgram& device_program(rh_schema* s, int device);
 uint64_t spec_min_records();
 // Specialised kernels of this schema on `device` (engine_kernels.cpp): never blocks on a compile unless the policy says so.
-const SpecKernel& spec_kernel(rh_schema* s, int device, rh::CompilePolicy policy, bool encode = false, bool want_fused = false, bool want_ranged = false);
+const SpecKernel& spec_kernel(rh_schema* s, int device, rh::CompilePolicy policy, bool encode = false, bool want_fused = false, bool want_ranged = false,
+                              bool want_lean = false);
+// The roads of the lean pair (rh_lean_counters, include/ruhvro_hip.h): counters of their own, nothing of rh_engine_counters moves
+enum LeanCounter { LC_LEAN_CALLS = 0, LC_PROBES, LC_PROBES_CLEAN, LC_PROBES_DIRTY, LC_FALLBACKS, LC_RERUNS, LC_NEED_RANGED, LC_NEED_WIDE_INDEX,
+                   LC_TWO_PASS_REPEATS, LC_CAPACITY_TAILS, LC_ASYNC_SETTLED, LC_COUNT };
+extern std::atomic<uint64_t> g_lean_counters[LC_COUNT];
+inline void lean_count(int which, uint64_t by = 1) { g_lean_counters[which].fetch_add(by, std::memory_order_relaxed); }
 // What a call of `n` records may spend on kernels this schema does not have yet.
 rh::CompilePolicy compile_policy(int mode, uint64_t n);
 int launch_module(hipFunction_t f, const rh::KParams& P, uint32_t grid, uint32_t block, uint32_t lds, hipStream_t stream,

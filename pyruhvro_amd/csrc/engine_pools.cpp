@@ -18,6 +18,7 @@ Pool& pin_pool() { static Pool* p = new Pool(true); return *p; }
 CtrlPool& ctrl_pool() { static CtrlPool* p = new CtrlPool(); return *p; }
 
 std::atomic<uint64_t> g_counters[RH_CTR_COUNT];
+std::atomic<uint64_t> g_lean_counters[LC_COUNT];
 
 char* dup_msg(const std::string& s) {
   char* p = (char*)std::malloc(s.size() + 1);

@@ -16,6 +16,7 @@
 #include <sys/stat.h>
 #include <unistd.h>
 
+#include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -68,24 +69,32 @@ int spec_tile_records() {
 // code paths of the device headers that are staged for an A/B on the GPU (`#ifdef RH_V_NAME`; each has its own
 // kernel-cache entry, since the key hashes the source).  Unset = the validated default kernels, byte for byte.
 // A variant that wins is made the default and its #ifdef removed; one that loses is deleted (scripts/gpu_ab.sh).
+// (generate_lean_source: LEN16 and INT28 count as named, whatever the variable says)
+static thread_local bool t_lean = false;
+
 static void emit_variant_defines(std::ostringstream& o) {
   const char* e = std::getenv("RUHVRO_HIP_VARIANT");
-  if (!e) return;
+  std::vector<std::string> names;
   std::string name;
-  for (const char* p = e;; p++) {
+  for (const char* p = e ? e : "";; p++) {
     if (*p == ',' || *p == 0) {
       bool ok = !name.empty();
       for (char ch : name) ok = ok && ((ch >= 'A' && ch <= 'Z') || (ch >= '0' && ch <= '9') || ch == '_');
-      if (ok) o << "#define RH_V_" << name << " 1\n";
+      if (ok) names.push_back(name);
       name.clear();
       if (*p == 0) break;
     } else {
       name.push_back(*p);
     }
   }
+  if (t_lean)
+    for (const char* n : {"LEN16", "INT28"})
+      if (std::find(names.begin(), names.end(), n) == names.end()) names.push_back(n);
+  for (const std::string& n : names) o << "#define RH_V_" << n << " 1\n";
 }
 
 static bool variant_on(const char* name) {
+  if (t_lean && (!std::strcmp(name, "LEN16") || !std::strcmp(name, "INT28"))) return true;
   const char* e = std::getenv("RUHVRO_HIP_VARIANT");
   if (!e) return false;
   const std::string all = std::string(",") + e + ",";
@@ -759,8 +768,17 @@ std::string generate_encode_source(const CompiledSchema& cs, unsigned parts) {
   return o.str();
 }
 
+bool schema_has_lean(const CompiledSchema& cs) { return (cs.K > 0 || cs.size_always) && !cs.wide; }
+
+std::string generate_lean_source(const CompiledSchema& cs, unsigned parts) {
+  if (!schema_has_lean(cs)) return "";
+  struct Scope { Scope() { t_lean = true; } ~Scope() { t_lean = false; } } lean;
+  return generate_kernel_source(cs, parts);
+}
+
 std::string generate_part_source(const CompiledSchema& cs, int part) {
   if (part < 0 || part >= KP_COUNT) return "";
+  if (part == KP_SIZE_L || part == KP_EMIT_L) return generate_lean_source(cs, 1u << (part == KP_SIZE_L ? KP_SIZE : KP_EMIT));
   if (part == KP_FUSED && cs.K > 64) return "";
   if (kernel_part_is_encode(part)) return (cs.encode_unsupported.empty() && !cs.projected) ? generate_encode_source(cs, 1u << part) : std::string();      // (projection is decode only)
   return generate_kernel_source(cs, 1u << part);

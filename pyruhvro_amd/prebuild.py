@@ -3,6 +3,13 @@
 hiprtc cross-compiles gfx950 without a GPU, so this runs in the build container; the cache travels
 with the tree to the GPU box, where the engine then only loads code objects.  Cache entries are keyed
 by a content hash of the generated source + the device headers, so stale entries are never used.
+
+rh_schema_prebuild compiles every kernel of a schema: the default pair, the single-pass kernel, the ranged pair and the
+Arrow -> Avro pair (RUHVRO_HIP_PREBUILD_FUSED=0 / _RANGED=0 leave those two to their first use), and with
+RUHVRO_HIP_PREBUILD_LEAN=1 the lean pair -- the default pair once more behind walk.h's narrow single-read forms, what the
+benchmark's batches of short varints run on (include/ruhvro_hip.h).  `python -m pyruhvro_amd.prebuild` sets it: the lean pair
+of the benchmark schemas is warm too.  Without it the pair is compiled in the background behind a schema's first qualifying
+call.
 """
 from __future__ import annotations
 
@@ -95,6 +102,7 @@ def benchmark_schemas() -> List[str]:
 
 
 if __name__ == "__main__":
+    os.environ.setdefault("RUHVRO_HIP_PREBUILD_LEAN", "1")
     errs = prebuild_many(benchmark_schemas(), verbose=True)
     for e in errs:
         print(e[:2000])

@@ -104,8 +104,10 @@ if __name__ == "__main__":
     with_fused = list(dict.fromkeys(single_pass_schemas()))
     rest = [s for s in dict.fromkeys(known_schemas()) if s not in set(with_fused)]
     rest.sort(key=len, reverse=True)            # (the widest schemas first: one of their kernels alone takes hiprtc minutes)
+    os.environ["RUHVRO_HIP_PREBUILD_LEAN"] = "1"      # (the lean pair: for these schemas only -- the benchmark's and the lean tests')
     errs = prebuild_many(with_fused, verbose=True)
     os.environ["RUHVRO_HIP_PREBUILD_FUSED"] = "0"
+    os.environ["RUHVRO_HIP_PREBUILD_LEAN"] = "0"
     errs += prebuild_many(rest, verbose=True)
     errs += prebuild_many(known_projections(), verbose=True)      # (without their single-pass kernel: compiled on first request)
     errs += prebuild_many([("resolve", w, r) for w, r in known_resolutions()], verbose=True)
