@@ -400,6 +400,48 @@ int rh_decode_device_tolerant(const rh_schema* s, const void* d_data, const void
                               uint64_t num_chunks, const rh_opts* opts, rh_device_result** out, rh_stats* stats, char** err,
                               uint64_t max_errors, rh_record_errors** errors);
 
+/* Avro object container files.  Added WITHOUT a change of RH_ABI_VERSION (7): a caller discovers these entry
+ * points by the presence of the symbols (dlsym).
+ *
+ * rh_container_scan parses the framing of a container held in host memory -- the header (magic, metadata map, sync marker) and
+ * the chain of blocks -- without touching a device: every read is checked against `len`.  It fails with RH_ERR_DECODE and a
+ * message that starts with "container: " (naming the block index where there is one) for a bad magic, a truncated header, a
+ * header without avro.schema, a negative count or size, a size past the end of the file, a sync marker that does not match,
+ * bytes left after the last complete block, and a codec other than "null" / "deflate".  The accessors' pointers belong to the
+ * info object (rh_container_info_free).  The block table: the payload of block b is bytes [start[b], end[b]) of the file and
+ * its first record has index first[b]; first[nb] = n.  A block without records and a file without blocks are legal.
+ * rh_container_info_metadata_*: the header's entries other than avro.schema and avro.codec, in file order. */
+typedef struct rh_container_info rh_container_info;
+int rh_container_scan(const uint8_t* data, uint64_t len, rh_container_info** info, char** err);
+const char* rh_container_info_schema(const rh_container_info* i, uint64_t* len);
+const char* rh_container_info_codec(const rh_container_info* i);       /* "null" when the header names none */
+const uint8_t* rh_container_info_sync(const rh_container_info* i);     /* 16 bytes */
+uint64_t rh_container_info_blocks(const rh_container_info* i);
+uint64_t rh_container_info_records(const rh_container_info* i);
+int rh_container_info_table(const rh_container_info* i, const uint64_t** start, const uint64_t** end, const uint64_t** first);
+uint32_t rh_container_info_metadata_count(const rh_container_info* i);
+int rh_container_info_metadata_get(const rh_container_info* i, uint32_t k, const char** key, const uint8_t** value, uint64_t* value_len);
+void rh_container_info_free(rh_container_info* i);
+/* The blocks call: `data` (host memory, `len` bytes) holds UNCOMPRESSED block payloads at [start[b], end[b]) -- a "null"-codec
+ * file as it is with the table of rh_container_scan, or a caller's own buffer of inflated blocks (ascending, not overlapping;
+ * the C ABI has no codec of its own).  The buffer and the table are uploaded once; a split kernel (one lane per block) walks
+ * every block's records with the WRITER's schema and leaves their offsets on the device; the device-input decode of
+ * rh_decode_device then runs on them.  The batches are those of rh_decode over the same records: same chunk rule, any kernel
+ * mode, `s` plain, projected (rh_schema_project) or resolved (rh_schema_resolve) -- the split always walks the plain schema
+ * such an `s` was made from.  A malformed record fails the call with rh_decode's message for the lowest failing record
+ * (RH_ERR_DECODE); a block whose records do not end where the block does fails it with "container: block b: its N records end
+ * at byte X of Y"; a block of 4 GiB - 16 bytes or more, or one whose count cannot fit its size, is refused likewise.  One
+ * device: rh_opts.devices (multi-device), RH_ASYNC and chunk_rows are refused with RH_ERR_ARGUMENT.  n = 0 gives one empty batch.
+ * rh_decode_blocks exports to host memory as rh_decode_packed does; rh_decode_blocks_device leaves the buffers in HBM (the
+ * result owns the uploaded bytes too).  rh_split_last_ms: GPU time of the most recent call's split kernel in this process. */
+int rh_decode_blocks(const rh_schema* s, const uint8_t* data, uint64_t len, const uint64_t* start, const uint64_t* end,
+                     const uint64_t* first, uint64_t nb, uint64_t num_chunks, const rh_opts* opts, struct ArrowArray* out_chunks,
+                     uint32_t* out_k, rh_stats* stats, char** err);
+int rh_decode_blocks_device(const rh_schema* s, const uint8_t* data, uint64_t len, const uint64_t* start, const uint64_t* end,
+                            const uint64_t* first, uint64_t nb, uint64_t num_chunks, const rh_opts* opts, rh_device_result** out,
+                            rh_stats* stats, char** err);
+float rh_split_last_ms(void);
+
 /* Measurement hook, not part of the drop-in surface: the host-side gather of a `shards`-GPU rh_decode call (every shard's
  * record slices copied into its staging buffer by its own host thread + `threads_per_shard` helpers, all shards at once)
  * without the GPUs -- pageable destinations (pinned = 0, runs on a box with no device), pinned ones (1), or pageable ones placed

@@ -3,8 +3,13 @@
 Same five functions as the reference's PyO3 module (src/lib.rs:150-158); the three decode functions also take the
 keyword-only extensions ``columns=[...]`` (decode only those top-level fields) and ``reader_schema=`` (decode
 writer-encoded records into an evolved schema).  Beside them the tolerant decode: the
-``*_tolerant`` functions replace malformed records by ``placeholder_datum(schema)`` and report all of them."""
+``*_tolerant`` functions replace malformed records by ``placeholder_datum(schema)`` and report all of them; and the Avro
+object container files: ``container_info`` / ``read_container`` / ``read_container_to_device`` / ``write_container``."""
 from pyruhvro_amd import (  # noqa: F401
+    container_info,
+    read_container,
+    read_container_to_device,
+    write_container,
     deserialize_array_tolerant,
     deserialize_array_threaded_tolerant,
     deserialize_binary_array_tolerant,

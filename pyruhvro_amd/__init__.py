@@ -405,7 +405,10 @@ __all__ = [
     "deserialize_binary_array", "set_devices", "kernels_ready", "prebuild", "deserialize_to_device",
     "placeholder_datum", "validate_records", "RecordError", "deserialize_array_tolerant", "deserialize_array_threaded_tolerant",
     "deserialize_binary_array_tolerant",
+    "container_info", "read_container", "read_container_to_device", "write_container", "ContainerInfo",
 ]
+
+from .container import ContainerInfo, container_info, read_container, read_container_to_device, write_container  # noqa: E402
 
 
 def __getattr__(name):      # (RecordError lives beside the ctypes wrappers that build it; cabi needs numpy, imported on first use)

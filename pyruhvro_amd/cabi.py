@@ -788,3 +788,116 @@ class PreparedDeviceDecode:
         if rc != RH_OK:
             _raise(rc, self._err)
         return _import_chunks(arr, k, self._schema.arrow_schema)
+
+
+# Avro object container files (include/ruhvro_hip.h): symbols added without a change of the ABI version, looked
+# up by name when first asked for.
+def _container_sym(name: str, restype, argtypes):
+    f = getattr(lib(), name, None)          # (ctypes: dlsym)
+    if f is None:
+        raise RuntimeError(f"libruhvro_hip.so has no {name}: the library was built before container reads")
+    f.restype, f.argtypes = restype, argtypes
+    return f
+
+
+def _u8(buf) -> np.ndarray:
+    a = np.ascontiguousarray(buf, dtype=np.uint8)
+    return a if a.size else np.zeros(1, dtype=np.uint8)      # (an addressable byte; the length is passed separately)
+
+
+def container_scan(buf: np.ndarray) -> dict:
+    """rh_container_scan over a uint8 array -> {"schema", "codec", "sync", "metadata", "start", "end", "first"}: the header and
+    the block table (uint64 arrays; first has one entry more than there are blocks, first[-1] = the number of records).  Raises
+    ValueError("container: ...") for a malformed file.  Needs no device."""
+    scan = _container_sym("rh_container_scan", C.c_int, [C.c_void_p, C.c_uint64, C.POINTER(C.c_void_p), C.POINTER(C.c_char_p)])
+    n = int(np.asarray(buf).size)
+    a = _u8(buf)
+    info, err = C.c_void_p(), C.c_char_p()
+    rc = scan(a.ctypes.data, n, C.byref(info), C.byref(err))
+    if rc != RH_OK:
+        _raise(rc, err)
+    h = info.value
+    try:
+        slen = C.c_uint64()
+        p = _container_sym("rh_container_info_schema", C.c_void_p, [C.c_void_p, C.POINTER(C.c_uint64)])(h, C.byref(slen))
+        schema = C.string_at(p, slen.value).decode("utf-8")
+        codec = C.string_at(_container_sym("rh_container_info_codec", C.c_void_p, [C.c_void_p])(h)).decode("utf-8", "replace")
+        sync = C.string_at(_container_sym("rh_container_info_sync", C.c_void_p, [C.c_void_p])(h), 16)
+        nb = int(_container_sym("rh_container_info_blocks", C.c_uint64, [C.c_void_p])(h))
+        ps, pe, pf = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        table = _container_sym("rh_container_info_table", C.c_int, [C.c_void_p] + [C.POINTER(C.c_void_p)] * 3)
+        if table(h, C.byref(ps), C.byref(pe), C.byref(pf)) != RH_OK:
+            raise RuntimeError("rh_container_info_table failed")
+
+        def arr(ptr, count):
+            return np.frombuffer(C.string_at(ptr, 8 * count), dtype=np.uint64).copy() if count else np.zeros(0, dtype=np.uint64)
+        start, end, first = arr(ps, nb), arr(pe, nb), arr(pf, nb + 1)
+        meta = {}
+        get = _container_sym("rh_container_info_metadata_get", C.c_int,
+                             [C.c_void_p, C.c_uint32, C.POINTER(C.c_char_p), C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)])
+        for k in range(_container_sym("rh_container_info_metadata_count", C.c_uint32, [C.c_void_p])(h)):
+            key, val, vlen = C.c_char_p(), C.c_void_p(), C.c_uint64()
+            if get(h, k, C.byref(key), C.byref(val), C.byref(vlen)) != RH_OK:
+                raise RuntimeError("rh_container_info_metadata_get failed")
+            meta[key.value.decode("utf-8", "replace")] = C.string_at(val, vlen.value) if vlen.value else b""
+        return {"schema": schema, "codec": codec, "sync": sync, "metadata": meta, "start": start, "end": end, "first": first}
+    finally:
+        _container_sym("rh_container_info_free", None, [C.c_void_p])(h)
+
+
+_BLOCKS_LEAD = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.POINTER(RhOpts)]
+
+
+def _blocks_args(data, start, end, first):
+    n = int(np.asarray(data).size)
+    data = _u8(data)
+    start = np.ascontiguousarray(start, dtype=np.uint64)
+    end = np.ascontiguousarray(end, dtype=np.uint64)
+    first = np.ascontiguousarray(first, dtype=np.uint64)
+    if len(start) != len(end) or len(first) != len(start) + 1:
+        raise ValueError("container: the block table needs as many starts as ends and one more first-record index")
+    one = np.zeros(1, dtype=np.uint64)
+    return (data, start if len(start) else one, end if len(end) else one, first), n, len(start)
+
+
+def decode_blocks(data, start, end, first, schema_json: str, num_chunks: int, device: int = -1, want_stats: bool = False,
+                  kernel: int = KERNEL_AUTO, *, columns=None, reader_schema=None):
+    """rh_decode_blocks: host bytes that hold uncompressed Avro container blocks at start[b] .. end[b], with first[b] the index
+    of each block's first record -> list[RecordBatch], the batches of decode_packed over the same records."""
+    s = Schema.get(schema_json, columns, reader_schema)
+    fn = _container_sym("rh_decode_blocks", C.c_int, _BLOCKS_LEAD + [C.POINTER(ArrowArray), C.POINTER(C.c_uint32), C.POINTER(RhStats),
+                                                                     C.POINTER(C.c_char_p)])
+    keep, nbytes, nb = _blocks_args(data, start, end, first)
+    n = int(keep[3][-1])
+    k = lib().rh_clamp_chunks(n, num_chunks)
+    arr = (ArrowArray * k)()
+    out_k, st, err = C.c_uint32(), RhStats(), C.c_char_p()
+    opts, _keep = make_opts(device, kernel)
+    rc = fn(s.handle, keep[0].ctypes.data, nbytes, keep[1].ctypes.data, keep[2].ctypes.data, keep[3].ctypes.data, nb, num_chunks,
+            C.byref(opts), arr, C.byref(out_k), C.byref(st), C.byref(err))
+    if rc != RH_OK:
+        _raise(rc, err)
+    out = _import_chunks(arr, out_k.value, s.arrow_schema)
+    return (out, st.as_dict()) if want_stats else out
+
+
+def decode_blocks_device(data, start, end, first, schema_json: str, num_chunks: int, device: int = -1, stream: int = 0,
+                         kernel: int = KERNEL_AUTO, *, columns=None, reader_schema=None) -> DeviceResult:
+    """rh_decode_blocks_device: decode_blocks with the Arrow buffers left in HBM (the result owns the uploaded bytes too)."""
+    s = Schema.get(schema_json, columns, reader_schema)
+    fn = _container_sym("rh_decode_blocks_device", C.c_int, _BLOCKS_LEAD + [C.POINTER(C.c_void_p), C.POINTER(RhStats), C.POINTER(C.c_char_p)])
+    keep, nbytes, nb = _blocks_args(data, start, end, first)
+    out, st, err = C.c_void_p(), RhStats(), C.c_char_p()
+    opts, _keep = make_opts(device, kernel, stream)
+    rc = fn(s.handle, keep[0].ctypes.data, nbytes, keep[1].ctypes.data, keep[2].ctypes.data, keep[3].ctypes.data, nb, num_chunks,
+            C.byref(opts), C.byref(out), C.byref(st), C.byref(err))
+    if rc != RH_OK:
+        _raise(rc, err)
+    r = DeviceResult(out.value, s, st.as_dict())
+    r._want_stats = True
+    return r
+
+
+def split_last_ms() -> float:
+    """rh_split_last_ms: GPU time of the split kernel of this process's most recent container read."""
+    return float(_container_sym("rh_split_last_ms", C.c_float, [])())

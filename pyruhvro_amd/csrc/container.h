@@ -1,0 +1,43 @@
+// Avro object container files (rh_decode_blocks): parameters of the split kernel (container.hip), shared by
+// host and device code.  Not one of the headers the specialised kernels include: the kernel-cache key does not see this file.
+#pragma once
+#include "program.h"
+
+namespace rh {
+
+// Beside program.h's ErrCode, the way F_DROP lives in walk_drop.h: a block whose records do not end where the block does.
+// detail = the byte of the block's payload at which its records ended.
+constexpr uint32_t E_BLOCK_END = 0x100;
+
+// What a failing lane leaves for its block (zero at launch: code 0 = the block is fine).
+struct SplitErr {
+  uint32_t code;     // ErrCode, or E_BLOCK_END
+  uint32_t pad;
+  int64_t detail;
+};
+
+// Order of the failures of one call: a malformed record r has key 2 r + 1, a block that does not end where its records do
+// has key 2 first[b + 1] -- behind its own last record, in front of the next block's first.  The lowest key wins (atomicMax of
+// its complement, as KParams::first_bad).
+RH_HD inline unsigned long long split_key_record(uint64_t rec) { return 2ull * rec + 1ull; }
+RH_HD inline unsigned long long split_key_block(uint64_t first_next) { return 2ull * first_next; }
+
+// rh_k_split: one lane per block, 256 blocks per workgroup; the careful counters-only walk of the writer's plain program, once
+// per record of the block, from global memory.
+struct SParams {
+  const uint8_t* data;       // the uploaded file (or the inflated blocks back to back), 16-byte aligned
+  uint64_t data_len;         // readable bytes at data
+  const uint64_t* start;     // [nb] first byte of every block's payload
+  const uint64_t* end;       // [nb] the byte behind it (end - start < 4 GiB - 16)
+  const uint64_t* first;     // [nb + 1] index of every block's first record; first[nb] = n
+  uint32_t nb;
+  int32_t list_depth;
+  const Op* prog;
+  const uint32_t* sym_off;
+  const uint8_t* sym_data;
+  uint64_t* offsets;         // out [n + 1]: record i spans offsets[i] .. offsets[i + 1] (a block's last record runs on to the next block's first)
+  SplitErr* err;             // out [nb]
+  unsigned long long* first_bad;   // [0] ~(lowest failure key), 0 if none
+};
+
+}  // namespace rh

@@ -1,0 +1,128 @@
+// CDNA4 (gfx950) kernel of the container read (rh_decode_blocks).
+//
+//   rh_k_split   "blocks" -> "record offsets".  An Avro container block says "N records, M bytes" and nothing says where record
+//                j starts: the only way to find out is to walk records 0 .. j - 1 with the writer's schema.  One lane per block
+//                runs the generic interpreter's CAREFUL walk with nothing stored and nothing counted (the walk of rh_k_validate:
+//                every op the way walk_drop.h runs the ops of a dropped field) once per record of its block, from global
+//                memory, and notes where every record began.  The program counter is wave-uniform; a lane whose block has
+//                fewer records than its neighbours' sits the other iterations out.
+// The walk reads every byte once, one dependent stream per lane, and a wavefront takes as long as its fullest block: the
+// parallelism is the number of blocks ("What bounds it").
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#define RH_DEEP 1      // as the interpreter of kernels.hip: any nesting the schema front-end accepts
+
+#include "kernel_common.h"
+#include "program.h"
+#include "walk.h"
+#include "walk_drop.h"
+#include "container.h"
+
+namespace rh {
+
+// what DropCtx needs of the walk's context (validate.hip VCtx): list framing and the enum symbols
+struct SCtx {
+  static constexpr bool kWide = true;
+  static constexpr bool kSkip = false;
+  static constexpr bool kEnumImm = false;
+  static constexpr bool kWaveCtr = false;
+  static __device__ __forceinline__ bool enum_sym(int, uint32_t, uint32_t&, uint64_t&) { return false; }
+  uint32_t* rem;             // LDS [depth][kBlock]
+  const uint32_t* sym_off;
+  const uint8_t* sym_data;
+  uint32_t lrow, tid, lane;
+  bool wave_live;
+  __device__ __forceinline__ uint32_t& remaining(int d) const { return rem[d * kBlock + tid]; }
+};
+
+typedef const __attribute__((address_space(4))) Op* SProgPtr;
+__device__ __forceinline__ Op s_ld_op(SProgPtr p) {
+  Op o;
+  o.code = p->code; o.flags = p->flags; o.dom = p->dom; o.a = p->a; o.b = p->b; o.c = p->c;
+  o.buf0 = p->buf0; o.buf1 = p->buf1; o.buf2 = p->buf2; o.node = p->node;
+  return o;
+}
+
+// one record per live lane: the program, every op counters-only and careful (validate.hip validate_walk)
+template <class Src>
+__device__ __forceinline__ void split_walk(const Op* program, const SCtx& c, const Src& src, Lane& L) {
+  const SProgPtr prog = reinterpret_cast<SProgPtr>(reinterpret_cast<uintptr_t>(program));
+  int pc = 0;
+  for (;;) {
+    pc = __builtin_amdgcn_readfirstlane(pc);
+    const Op op = s_ld_op(prog + pc);
+    if (op.code == OP_END) return;
+    int npc = op.code == OP_LIST_TAIL ? op.b : pc + 1;      // LIST_TAIL goes back to its LIST_NEXT
+    if (op.code > OP_BIN) return;
+    if (!run_dropped<false, true>(c, src, L, op)) npc = op.b;      // no lane has an item left: to LIST_END
+    pc = npc;
+  }
+}
+
+extern "C" __global__ void __launch_bounds__(kBlock) rh_k_split(SParams S) {
+  extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+  const uint32_t tid = threadIdx.x, lane = tid & 63;
+  const uint32_t depth = (uint32_t)(S.list_depth > 0 ? S.list_depth : 1);
+  uint32_t* const rem = reinterpret_cast<uint32_t*>(smem);
+  for (uint32_t d = 0; d < depth; d++) rem[d * kBlock + tid] = 0;
+  __syncthreads();
+
+  const uint64_t b = (uint64_t)blockIdx.x * kBlock + tid;
+  const bool mine = b < (uint64_t)S.nb;
+  uint64_t st = 0, en = 0, f0 = 0, f1 = 0;
+  if (mine) { st = S.start[b]; en = S.end[b]; f0 = S.first[b]; f1 = S.first[b + 1]; }
+  const uint64_t cnt = f1 - f0;
+  // the lane's source is based at its own block: cursors stay 32-bit (the host refuses a block of 4 GiB - 16 or more)
+  const uint64_t base = st & ~15ull;
+  const GlobalSrc src{S.data + base, S.data_len - base};
+  const uint32_t cur0 = (uint32_t)(st - base), end = cur0 + (uint32_t)(en - st);
+
+  SCtx c;
+  c.rem = rem; c.sym_off = S.sym_off; c.sym_data = S.sym_data;
+  c.lrow = tid; c.tid = tid; c.lane = lane; c.wave_live = true;
+  Lane L;
+  L.cur = cur0; L.end = end; L.err = 0; L.edetail = 0;
+  uint32_t code = 0;
+  int64_t detail = 0;
+  unsigned long long key = 0;
+  uint64_t j = 0;
+  for (;;) {
+    const bool go = mine && code == 0 && j < cnt;
+    if (!__any(go)) break;      // (wave-uniform)
+    const uint32_t at = L.cur;
+    if (go) S.offsets[f0 + j] = st + (uint64_t)(at - cur0);
+    L.err = 0; L.edetail = 0;
+    L.live = go; L.pres = go; L.redo = false; L.la = 0;
+    L.pstk = 0; L.lstk = 0; L.sstk = 0;
+    split_walk(S.prog, c, src, L);
+    if (go && L.err) { code = L.err; detail = L.edetail; key = split_key_record(f0 + j); }
+    if (!go) L.cur = at;        // (a lane that sat the record out stays where it was)
+    j += go ? 1u : 0u;
+  }
+  if (mine && code == 0 && L.cur != end) { code = E_BLOCK_END; detail = (int64_t)(L.cur - cur0); key = split_key_block(f1); }
+  if (mine && code != 0) {
+    SplitErr e; e.code = code; e.pad = 0; e.detail = detail;
+    S.err[b] = e;
+    atomicMax(S.first_bad, ~key);
+  }
+  if (mine && b + 1 == (uint64_t)S.nb) S.offsets[f1] = en;      // offsets[n]: the last record ends with the last block
+}
+
+}  // namespace rh
+
+// --------------------------------------------------------------------------
+// launcher (engine_container.cpp)
+// --------------------------------------------------------------------------
+extern "C" uint32_t rh_split_lds_bytes(int list_depth) { return (uint32_t)(list_depth > 0 ? list_depth : 1) * rh::kBlock * 4; }
+
+extern "C" int rh_launch_split(const rh::SParams* S, void* stream) {
+  (void)hipGetLastError();
+  if (S->nb == 0) return 0;
+  const uint32_t lds = rh_split_lds_bytes(S->list_depth);
+  int e = (int)hipFuncSetAttribute(reinterpret_cast<const void*>(rh::rh_k_split), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+  if (e) return e;
+  const uint32_t nblocks = (S->nb + rh::kBlock - 1) / rh::kBlock;
+  hipLaunchKernelGGL(rh::rh_k_split, dim3(nblocks), dim3(rh::kBlock), lds, (hipStream_t)stream, *S);
+  return (int)hipGetLastError();
+}

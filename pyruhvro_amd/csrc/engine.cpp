@@ -227,6 +227,7 @@ rh_schema* rh_schema_resolve(const rh_schema* writer, const char* reader_json, s
 
 void rh_schema_free(rh_schema* s) {
   if (!s) return;
+  rh_schema_free(s->plain_parent);      // (a projection's / resolution's plain writer schema: engine_container.cpp)
   for (auto& kv : s->dev) {
     (void)hipFree(kv.second.prog);
     (void)hipFree(kv.second.sym_off);

@@ -399,6 +399,9 @@ struct rh_schema {
   // Tolerant decode: the schema's placeholder datum (engine_tolerant.cpp placeholder_datum), built on first use under `mu`
   std::vector<uint8_t> placeholder;
   bool placeholder_done = false;
+  // Container reads (engine_container.cpp): the plain compile of a projection's / resolution's writer text -- the program the
+  // split kernel walks -- made on first use under `mu`, freed with this schema
+  rh_schema* plain_parent = nullptr;
   uint32_t single_cooldown = 0, single_backoff = 0;      // calls the single pass sits out after a fail-over (8, 16, ... 1024; a success clears it)
 };
 
@@ -540,6 +543,8 @@ struct rh_device_result {
   // A tolerant call that repaired its input (rh_decode_device_tolerant): the patched payload and offsets the call decoded.
   // Nothing in the result points into them; they are kept so that the result owns every byte its call read.
   rhe::Lease patched_data, patched_offsets;
+  // A container read (rh_decode_blocks*): the uploaded file and the record offsets the split kernel made, kept likewise
+  rhe::Lease container_data, container_offsets;
   std::vector<hipEvent_t> join_events;  // recorded on the internal streams, waited for by the caller's stream (recycled on free)
 
   rh_device_result();

@@ -1,0 +1,184 @@
+"""Container reads against the list and BinaryArray paths IN THE SAME RUN (bench.py does not know containers).
+
+    python scripts/container_bench.py [--records 10000000] [--reps 7] [--out profiles/container_full10m.json]
+
+`--records` records of the `full` workload, 8 chunks, specialised kernels, warm, host in -> host out:
+  list          deserialize_array_threaded(list[bytes])         the yardsticks: unchanged paths, with their run-to-run spread
+  binary_array  deserialize_binary_array(BinaryArray)
+  null_64k      read_container of the same records as a `null` container with ~64 KB blocks
+  null_1m       ... with ~1 MB blocks
+  deflate_64k   ... as a `deflate` container with ~64 KB blocks (inflated on the host with zlib, then the same blocks call)
+Every figure is the median of `--reps` calls: end-to-end wall time, and for the container reads the split kernel's own GPU time
+(rh_split_last_ms) next to the decode kernels' (size, scan, emit: rh_stats), and the host's share of one blocks call: inflating,
+the upload of the file (rh_stats.h2d_ms) and the export of the results to host memory (d2h_ms).  No threshold: the table prices the split walk.
+One JSON object on stdout, also written to --out; the Markdown table on stderr and into DESIGN.md 14, between its two marker
+lines (--design '' leaves the document alone; --from-json FILE rewrites the table from an earlier run's JSON without measuring).
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+import zlib
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for _p in (ROOT, os.path.join(ROOT, "tests")):
+    if _p not in sys.path:
+        sys.path.insert(0, _p)
+
+SYNC = bytes(range(16))
+
+
+def _zz(n: int) -> bytes:
+    z = n << 1
+    out = bytearray()
+    while z >= 0x80:
+        out.append((z & 0x7F) | 0x80)
+        z >>= 7
+    out.append(z)
+    return bytes(out)
+
+
+def container_of(schema: str, data, offsets, block_bytes: int, codec: str) -> tuple:
+    """The packed records (payload + n + 1 offsets) as a container of blocks of about `block_bytes` -> (bytes, number of blocks)."""
+    import numpy as np
+    out = bytearray(b"Obj\x01" + _zz(2))
+    for k, v in ((b"avro.schema", schema.encode()), (b"avro.codec", codec.encode())):
+        out += _zz(len(k)) + k + _zz(len(v)) + v
+    out += _zz(0) + SYNC
+    n = len(offsets) - 1
+    mv = memoryview(data)
+    r0, nb = 0, 0
+    while r0 < n:
+        r1 = int(np.searchsorted(offsets, int(offsets[r0]) + block_bytes, side="right")) - 1
+        r1 = min(max(r1, r0 + 1), n)
+        payload = mv[int(offsets[r0]):int(offsets[r1])]
+        if codec == "deflate":
+            c = zlib.compressobj(1, zlib.DEFLATED, -15)
+            payload = c.compress(payload) + c.flush()
+        out += _zz(r1 - r0) + _zz(len(payload))
+        out += payload
+        out += SYNC
+        r0 = r1
+        nb += 1
+    return bytes(out), nb
+
+
+BEGIN, END = "<!-- container_bench: table -->", "<!-- container_bench: end -->"
+
+
+def table(out: dict) -> str:
+    lst = out["calls"]["list"]["wall_ms"]
+    rows = ["| input | blocks | end to end ms (min - max) | vs list | split ms | split / end to end | size / scan / emit ms | inflate / upload / export ms |",
+            "|---|---|---|---|---|---|---|---|"]
+    for name, d in out["calls"].items():
+        k = (f"{d['split_ms']:.2f} | {100 * d['split_share_of_wall']:.1f} % | {d['size_ms']:.2f} / {d['scan_ms']:.2f} / {d['emit_ms']:.2f} | "
+             f"{d['inflate_ms']:.0f} / {d['upload_ms']:.0f} / {d['export_ms']:.0f}" if "split_ms" in d else "- | - | - | -")
+        rows.append(f"| {name} | {d.get('blocks', '-')} | {d['wall_ms']:.0f} ({d['wall_ms_min']:.0f} - {d['wall_ms_max']:.0f}) | "
+                    f"{d['wall_ms'] / lst:.2f} | {k} |")
+    return "\n".join(rows)
+
+
+def report(out: dict, design: str) -> None:
+    """The Markdown table on stderr, and between the two marker lines of DESIGN.md 14."""
+    t = table(out)
+    print(t, file=sys.stderr)
+    if design:
+        text = open(design).read()
+        i, j = text.index(BEGIN) + len(BEGIN), text.index(END)
+        open(design, "w").write(text[:i] + "\n" + t + "\n" + text[j:])
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--design", default=os.path.join(ROOT, "DESIGN.md"), help="the document whose table is rewritten ('' = none)")
+    ap.add_argument("--from-json", default=None, help="no measurement: the table of an earlier run's JSON")
+    ap.add_argument("--records", type=int, default=10_000_000)
+    ap.add_argument("--reps", type=int, default=7)
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "container_full10m.json"))
+    a = ap.parse_args()
+    if a.from_json:
+        report(json.load(open(a.from_json)), a.design)
+        return 0
+
+    import numpy as np
+    import pyarrow as pa
+    import torch  # noqa: F401  first: the engine shares torch's HIP runtime
+    from avrogen import fastgen
+    from avrogen.schemas import SCHEMAS
+    import pyruhvro_amd as P
+    from pyruhvro_amd import cabi
+
+    t_start = time.perf_counter()
+
+    def note(what):      # progress on stderr: the 10M run is minutes of host work (generating, framing, deflating) between figures
+        print(f"[{time.perf_counter() - t_start:6.1f} s] {what}", file=sys.stderr, flush=True)
+
+    schema = SCHEMAS["full"]
+    note(f"generating {a.records} records")
+    data, offsets = fastgen.generate("full", a.records)
+    out = {"workload": "full", "records": a.records, "payload_bytes": int(offsets[-1]), "chunks": 8, "reps": a.reps, "calls": {}}
+    old = P.set_kernel_mode("specialized")
+
+    def timed(fn, reps):
+        for _ in range(2):
+            fn()
+        ts = []
+        for _ in range(reps):
+            t0 = time.perf_counter()
+            b = fn()
+            ts.append((time.perf_counter() - t0) * 1e3)
+            del b
+        d = {"wall_ms": statistics.median(ts), "wall_ms_min": min(ts), "wall_ms_max": max(ts)}
+        d["spread"] = (d["wall_ms_max"] - d["wall_ms_min"]) / d["wall_ms"]
+        return d
+
+    note("list")
+    recs = fastgen.split(data, offsets)
+    out["calls"]["list"] = timed(lambda: P.deserialize_array_threaded(recs, schema, 8), a.reps)
+    del recs
+    note("binary_array")
+    arr = pa.LargeBinaryArray.from_buffers(pa.large_binary(), a.records, [None, pa.py_buffer(offsets.view(np.int64)), pa.py_buffer(data)])
+    out["calls"]["binary_array"] = timed(lambda: P.deserialize_binary_array(arr, schema, 8), a.reps)
+    del arr
+
+    for label, block_bytes, codec, reps in (("null_64k", 64 << 10, "null", a.reps), ("null_1m", 1 << 20, "null", a.reps),
+                                            ("deflate_64k", 64 << 10, "deflate", max(3, a.reps // 2))):
+        note(label)
+        blob, nb = container_of(schema, data, offsets, block_bytes, codec)
+        note(f"{label}: {nb} blocks, {len(blob)} bytes")
+        info = P.container_info(blob)
+        assert (info.num_blocks, info.num_records) == (nb, a.records)
+        buf = np.frombuffer(blob, dtype=np.uint8)
+
+        def kernels():      # the blocks call alone, for the kernels' own times (the deflate file: its inflated blocks)
+            from pyruhvro_amd import container as CT
+            t0 = time.perf_counter()
+            b, start, end = (CT._inflate(buf, info) if codec == "deflate" else (buf, info._start, info._end))
+            inflate_ms = (time.perf_counter() - t0) * 1e3
+            _, st = cabi.decode_blocks(b, start, end, info._first, schema, 8, kernel=cabi.KERNEL_SPECIALIZED, want_stats=True)
+            return {"split_ms": cabi.split_last_ms(), "size_ms": st["size_kernel_ms"], "scan_ms": st["scan_kernel_ms"], "emit_ms": st["emit_kernel_ms"],
+                    "inflate_ms": inflate_ms, "upload_ms": st["h2d_ms"], "export_ms": st["d2h_ms"], "blocks_call_ms": st["total_ms"]}
+        d = timed(lambda: P.read_container(blob, 8), reps)
+        ks = [kernels() for _ in range(3)]
+        for key in ks[0]:
+            d[key] = statistics.median(k[key] for k in ks)
+        d.update({"blocks": nb, "file_bytes": len(blob), "vs_list": d["wall_ms"] / out["calls"]["list"]["wall_ms"],
+                  "split_share_of_wall": d["split_ms"] / d["wall_ms"]})
+        out["calls"][label] = d
+        del blob, buf
+    P.set_kernel_mode(old)
+    note("done")
+
+    text = json.dumps(out, indent=1)
+    print(text)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        open(a.out, "w").write(text + "\n")
+    report(out, a.design)
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
