@@ -442,6 +442,52 @@ int rh_decode_blocks_device(const rh_schema* s, const uint8_t* data, uint64_t le
                             rh_stats* stats, char** err);
 float rh_split_last_ms(void);
 
+/* Deflate blocks inflated on the device ("Deflate blocks on the device").  Added WITHOUT a change of
+ * RH_ABI_VERSION (7), like the entry points above: a caller discovers them by the presence of the symbols (dlsym).
+ *
+ * rh_decode_cblocks / rh_decode_cblocks_device are rh_decode_blocks / rh_decode_blocks_device with a codec: for
+ * RH_CODEC_DEFLATE `start` / `end` delimit the COMPRESSED payloads -- raw deflate (RFC 1951), one stream per block, the table
+ * of rh_container_scan as it is.  The file is uploaded compressed; a size kernel walks every stream (one wavefront per block)
+ * and reports its inflated size and its verdict, the host lays the blocks out back to back, an emit kernel writes their bytes,
+ * and the call goes on as rh_decode_blocks does from its upload.  What is a valid stream is what zlib's inflate accepts.  A
+ * block that does not inflate fails the call with RH_ERR_DECODE before any record is walked, the lowest such block first:
+ * "container: block b: deflate: <reason>" for a malformed stream (the reasons: DESIGN.md 14), "... deflate: the stream ends
+ * before its final block", "... deflate: N bytes behind the end of the stream", "... deflate: it inflates to L bytes or more
+ * (a block of 4 GiB - 16 bytes or more is not supported)" with L = max_block_bytes (0: the engine's own limit, 4 GiB - 16).  The
+ * checks of rh_decode_blocks on a block's size and record count apply to the INFLATED sizes.  The refusals are those of
+ * rh_decode_blocks (devices, RH_ASYNC, chunk_rows); codec = RH_CODEC_NULL is rh_decode_blocks (max_block_bytes is not read). */
+#define RH_CODEC_NULL 0
+#define RH_CODEC_DEFLATE 1
+int rh_decode_cblocks(const rh_schema* s, const uint8_t* data, uint64_t len, const uint64_t* start, const uint64_t* end,
+                      const uint64_t* first, uint64_t nb, int codec, uint64_t max_block_bytes, uint64_t num_chunks, const rh_opts* opts,
+                      struct ArrowArray* out_chunks, uint32_t* out_k, rh_stats* stats, char** err);
+int rh_decode_cblocks_device(const rh_schema* s, const uint8_t* data, uint64_t len, const uint64_t* start, const uint64_t* end,
+                             const uint64_t* first, uint64_t nb, int codec, uint64_t max_block_bytes, uint64_t num_chunks,
+                             const rh_opts* opts, rh_device_result** out, rh_stats* stats, char** err);
+/* The inflate step alone, host in and host out: the nb streams at data[start[b] .. end[b]) inflated by the same two kernels.
+ * Returns RH_OK with one status PER BLOCK -- one launch gives the verdicts of thousands of damaged streams.  *out (malloc'd,
+ * release with rh_free_string) holds the accepted blocks back to back, block b at [out_start[b], out_end[b]); a failing block
+ * contributes zero bytes.  reason: which rule a malformed stream broke (RH_INFLATE_MALFORMED only; pyruhvro_amd/csrc/
+ * inflate_core.h R_*).  detail: RH_INFLATE_TRAILING -- the whole bytes behind the byte that holds the stream's
+ * last bit (zlib's unused_data); RH_INFLATE_TOO_LARGE -- the limit; RH_INFLATE_MALFORMED -- which code, for the rules about a
+ * code (0 code-length, 1 literal/length, 2 distance).  RH_INFLATE_INTERNAL is never returned: it fails the call. */
+#define RH_INFLATE_OK 0
+#define RH_INFLATE_MALFORMED 1
+#define RH_INFLATE_TRUNCATED 2
+#define RH_INFLATE_TRAILING 3
+#define RH_INFLATE_TOO_LARGE 4
+#define RH_INFLATE_INTERNAL 5
+typedef struct rh_inflate_status {
+  uint32_t code;
+  uint32_t reason;
+  uint64_t detail;
+} rh_inflate_status;
+int rh_inflate_blocks(const uint8_t* data, uint64_t len, const uint64_t* start, const uint64_t* end, uint64_t nb, uint64_t max_block_bytes,
+                      const rh_opts* opts, uint8_t** out, uint64_t* out_len, uint64_t* out_start, uint64_t* out_end,
+                      rh_inflate_status* status, char** err);
+/* The most recent device inflate of this process: GPU time of its two kernels, compressed bytes in, inflated bytes out. */
+void rh_inflate_last(float* size_ms, float* emit_ms, uint64_t* in_bytes, uint64_t* out_bytes);
+
 /* Measurement hook, not part of the drop-in surface: the host-side gather of a `shards`-GPU rh_decode call (every shard's
  * record slices copied into its staging buffer by its own host thread + `threads_per_shard` helpers, all shards at once)
  * without the GPUs -- pageable destinations (pinned = 0, runs on a box with no device), pinned ones (1), or pageable ones placed

@@ -901,3 +901,91 @@ def decode_blocks_device(data, start, end, first, schema_json: str, num_chunks: 
 def split_last_ms() -> float:
     """rh_split_last_ms: GPU time of the split kernel of this process's most recent container read."""
     return float(_container_sym("rh_split_last_ms", C.c_float, [])())
+
+
+# Deflate blocks inflated on the device (DESIGN.md 14): added like the entry points above, looked up by symbol.
+CODEC_NULL, CODEC_DEFLATE = 0, 1
+INFLATE_OK, INFLATE_MALFORMED, INFLATE_TRUNCATED, INFLATE_TRAILING, INFLATE_TOO_LARGE = 0, 1, 2, 3, 4
+_CBLOCKS_LEAD = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_uint64, C.c_uint64,
+                 C.POINTER(RhOpts)]
+
+
+class InflateStatus(C.Structure):
+    _fields_ = [("code", C.c_uint32), ("reason", C.c_uint32), ("detail", C.c_uint64)]
+
+
+def decode_cblocks(data, start, end, first, schema_json: str, num_chunks: int, codec: int = CODEC_DEFLATE, max_block_bytes: int = 0,
+                   device: int = -1, want_stats: bool = False, kernel: int = KERNEL_AUTO, *, columns=None, reader_schema=None):
+    """rh_decode_cblocks: decode_blocks over the blocks of a container as they are in the file -- for CODEC_DEFLATE start[b] ..
+    end[b] are the COMPRESSED payloads, inflated on the device."""
+    s = Schema.get(schema_json, columns, reader_schema)
+    fn = _container_sym("rh_decode_cblocks", C.c_int, _CBLOCKS_LEAD + [C.POINTER(ArrowArray), C.POINTER(C.c_uint32), C.POINTER(RhStats),
+                                                                       C.POINTER(C.c_char_p)])
+    keep, nbytes, nb = _blocks_args(data, start, end, first)
+    n = int(keep[3][-1])
+    k = lib().rh_clamp_chunks(n, num_chunks)
+    arr = (ArrowArray * k)()
+    out_k, st, err = C.c_uint32(), RhStats(), C.c_char_p()
+    opts, _keep = make_opts(device, kernel)
+    rc = fn(s.handle, keep[0].ctypes.data, nbytes, keep[1].ctypes.data, keep[2].ctypes.data, keep[3].ctypes.data, nb, codec,
+            max_block_bytes, num_chunks, C.byref(opts), arr, C.byref(out_k), C.byref(st), C.byref(err))
+    if rc != RH_OK:
+        _raise(rc, err)
+    out = _import_chunks(arr, out_k.value, s.arrow_schema)
+    return (out, st.as_dict()) if want_stats else out
+
+
+def decode_cblocks_device(data, start, end, first, schema_json: str, num_chunks: int, codec: int = CODEC_DEFLATE,
+                          max_block_bytes: int = 0, device: int = -1, stream: int = 0, kernel: int = KERNEL_AUTO, *, columns=None,
+                          reader_schema=None) -> DeviceResult:
+    """rh_decode_cblocks_device: decode_cblocks with the Arrow buffers left in HBM (the result owns the inflated bytes too)."""
+    s = Schema.get(schema_json, columns, reader_schema)
+    fn = _container_sym("rh_decode_cblocks_device", C.c_int, _CBLOCKS_LEAD + [C.POINTER(C.c_void_p), C.POINTER(RhStats), C.POINTER(C.c_char_p)])
+    keep, nbytes, nb = _blocks_args(data, start, end, first)
+    out, st, err = C.c_void_p(), RhStats(), C.c_char_p()
+    opts, _keep = make_opts(device, kernel, stream)
+    rc = fn(s.handle, keep[0].ctypes.data, nbytes, keep[1].ctypes.data, keep[2].ctypes.data, keep[3].ctypes.data, nb, codec,
+            max_block_bytes, num_chunks, C.byref(opts), C.byref(out), C.byref(st), C.byref(err))
+    if rc != RH_OK:
+        _raise(rc, err)
+    r = DeviceResult(out.value, s, st.as_dict())
+    r._want_stats = True
+    return r
+
+
+def inflate_blocks(data, start, end, max_block_bytes: int = 0, device: int = -1):
+    """rh_inflate_blocks: the raw-deflate streams at data[start[b] .. end[b]) inflated on the device -> (out, out_start, out_end,
+    status): the accepted blocks back to back (bytes), where each lies (uint64 arrays; a failing block is empty), and one
+    (code, reason, detail) per block (a structured array; code is one of INFLATE_*)."""
+    fn = _container_sym("rh_inflate_blocks", C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.POINTER(RhOpts),
+                                                       C.POINTER(C.c_void_p), C.POINTER(C.c_uint64), C.c_void_p, C.c_void_p, C.c_void_p,
+                                                       C.POINTER(C.c_char_p)])
+    n = int(np.asarray(data).size)
+    data = _u8(data)
+    start = np.ascontiguousarray(start, dtype=np.uint64)
+    end = np.ascontiguousarray(end, dtype=np.uint64)
+    if len(start) != len(end):
+        raise ValueError("container: the block table needs as many starts as ends")
+    nb = len(start)
+    out_start, out_end = np.zeros(max(nb, 1), dtype=np.uint64), np.zeros(max(nb, 1), dtype=np.uint64)
+    status = np.zeros(max(nb, 1), dtype=np.dtype([("code", np.uint32), ("reason", np.uint32), ("detail", np.uint64)]))
+    one = np.zeros(1, dtype=np.uint64)
+    out, out_len, err = C.c_void_p(), C.c_uint64(), C.c_char_p()
+    opts, _keep = make_opts(device, KERNEL_AUTO)
+    rc = fn(data.ctypes.data, n, (start if nb else one).ctypes.data, (end if nb else one).ctypes.data, nb, max_block_bytes, C.byref(opts),
+            C.byref(out), C.byref(out_len), out_start.ctypes.data, out_end.ctypes.data, status.ctypes.data, C.byref(err))
+    if rc != RH_OK:
+        _raise(rc, err)
+    try:
+        blob = C.string_at(out.value, out_len.value) if out_len.value else b""
+    finally:
+        lib().rh_free_string(C.cast(out, C.c_void_p))
+    return blob, out_start[:nb], out_end[:nb], status[:nb]
+
+
+def inflate_last() -> dict:
+    """rh_inflate_last: the most recent device inflate of this process -- GPU time of its two kernels, bytes in and out."""
+    fn = _container_sym("rh_inflate_last", None, [C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)])
+    a, b, c, d = C.c_float(), C.c_float(), C.c_uint64(), C.c_uint64()
+    fn(C.byref(a), C.byref(b), C.byref(c), C.byref(d))
+    return {"size_ms": a.value, "emit_ms": b.value, "in_bytes": c.value, "out_bytes": d.value}

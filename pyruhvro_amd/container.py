@@ -8,9 +8,11 @@
 A container block says "N records, M bytes" and nothing says where record j starts.  The file is uploaded as it is and a
 split kernel -- one lane per block -- walks the records with the writer's schema (the file's own, from its header) to find
 their offsets; the ordinary decode then runs on them.  ``columns=`` and ``reader_schema=`` mean what they mean for
-``deserialize_array_threaded``.  Codecs: ``null`` and ``deflate`` (inflated here with ``zlib``, block by block, into one
-buffer); anything else is refused.  The tolerant functions do not take containers: a malformed record loses its block's
-boundaries.
+``deserialize_array_threaded``.  Codecs: ``null`` and ``deflate``; anything else is refused.  A ``deflate`` file is inflated
+either here with ``zlib``, block by block, into one buffer (``inflate="host"``, the default), or on the device: the
+compressed file is uploaded as it is and two kernels inflate its blocks, one wavefront per block (``inflate="device"``, or
+``RUHVRO_HIP_INFLATE=device`` in the environment).  Both roads accept the same streams and raise the same messages.  The
+tolerant functions do not take containers: a malformed record loses its block's boundaries.
 """
 from __future__ import annotations
 
@@ -99,40 +101,61 @@ def _inflate(buf, info: ContainerInfo):
     return np.frombuffer(out, dtype=np.uint8) if out else np.zeros(0, dtype=np.uint8), start, end
 
 
-def _blocks(src, num_chunks, columns, reader_schema):
+def _inflate_road(inflate) -> str:
+    """``inflate=`` of a read: "host" or "device"; None reads RUHVRO_HIP_INFLATE (per call) and falls back to "host"."""
+    if inflate is None:
+        inflate = os.environ.get("RUHVRO_HIP_INFLATE") or "host"
+    if inflate not in ("host", "device"):
+        raise ValueError("container: inflate must be 'host' or 'device'")
+    return inflate
+
+
+def _blocks(src, num_chunks, columns, reader_schema, inflate=None):
+    """-> (info, buf, start, end, on_device): on_device = the blocks are still deflated, for the device to inflate."""
     import pyruhvro_amd as P
+    road = _inflate_road(inflate)                            # ValueError before any device work, for a `null` file too
     P._check_chunks(num_chunks)
     buf, info = _scan(src)                                   # ValueError "container: ..." before any device work
     P._get_schema(info.schema, columns, reader_schema)       # ValueError on a schema outside the decoder's subset, like every entry point
+    if info.codec == "deflate" and road == "device":
+        return info, buf, info._start, info._end, True
     if info.codec == "deflate":
         buf, start, end = _inflate(buf, info)
     else:
         start, end = info._start, info._end
-    return info, buf, start, end
+    return info, buf, start, end, False
 
 
-def read_container(src, num_chunks=1, *, columns=None, reader_schema=None):
+def read_container(src, num_chunks=1, *, columns=None, reader_schema=None, inflate=None):
     """Extension.  The records of the Avro object container ``src`` (a buffer-protocol object -- ``bytes``, ``bytearray``,
     ``memoryview``, ``mmap``, a numpy ``uint8`` array -- or a ``str`` / ``os.PathLike`` path, which is mapped) decoded into
     ``list[pyarrow.RecordBatch]``: exactly ``deserialize_array_threaded(records, info.schema, num_chunks, ...)`` over the
     file's records, without splitting them on the CPU.  The writer schema is the file's.  A malformed record raises what that
-    call raises for it; a malformed file raises ``ValueError`` starting with ``container: ``."""
+    call raises for it; a malformed file raises ``ValueError`` starting with ``container: ``.  ``inflate``: where a ``deflate``
+    file's blocks are inflated -- ``"host"`` (``zlib``), ``"device"`` (the GPU), ``None`` = ``RUHVRO_HIP_INFLATE`` or ``"host"``."""
     import pyruhvro_amd as P
     from . import cabi
-    info, buf, start, end = _blocks(src, num_chunks, columns, reader_schema)
+    info, buf, start, end, on_device = _blocks(src, num_chunks, columns, reader_schema, inflate)
+    if on_device:
+        return cabi.decode_cblocks(buf, start, end, info._first, info.schema, num_chunks, cabi.CODEC_DEFLATE, MAX_BLOCK_BYTES,
+                                   kernel=P._kernel_mode, columns=columns, reader_schema=reader_schema)
     return cabi.decode_blocks(buf, start, end, info._first, info.schema, num_chunks, kernel=P._kernel_mode, columns=columns,
                               reader_schema=reader_schema)
 
 
-def read_container_to_device(src, num_chunks=1, device: int = -1, *, columns=None, reader_schema=None):
+def read_container_to_device(src, num_chunks=1, device: int = -1, *, columns=None, reader_schema=None, inflate=None):
     """Extension.  ``read_container`` with the Arrow buffers left in HBM: a ``DeviceDecode`` as ``deserialize_to_device``
     returns (``.batches``, ``.to_host()``, every buffer a DLPack producer)."""
     import pyruhvro_amd as P
     from . import cabi
     from .device import DeviceDecode
-    info, buf, start, end = _blocks(src, num_chunks, columns, reader_schema)
-    r = cabi.decode_blocks_device(buf, start, end, info._first, info.schema, num_chunks, device=device, kernel=P._kernel_mode,
-                                  columns=columns, reader_schema=reader_schema)
+    info, buf, start, end, on_device = _blocks(src, num_chunks, columns, reader_schema, inflate)
+    if on_device:
+        r = cabi.decode_cblocks_device(buf, start, end, info._first, info.schema, num_chunks, cabi.CODEC_DEFLATE, MAX_BLOCK_BYTES,
+                                       device=device, kernel=P._kernel_mode, columns=columns, reader_schema=reader_schema)
+    else:
+        r = cabi.decode_blocks_device(buf, start, end, info._first, info.schema, num_chunks, device=device, kernel=P._kernel_mode,
+                                      columns=columns, reader_schema=reader_schema)
     return DeviceDecode(r, cabi.Schema.get(info.schema, columns, reader_schema).arrow_schema)
 
 

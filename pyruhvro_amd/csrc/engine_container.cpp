@@ -4,10 +4,13 @@
 #include "engine_internal.h"
 #include "container.h"
 #include "container_scan.h"
+#include "inflate.h"
 
 extern "C" {
 uint32_t rh_split_lds_bytes(int list_depth);
 int rh_launch_split(const rh::SParams* S, void* stream);
+int rh_launch_inflate_size(const rh::InflateParams* P, void* stream);
+int rh_launch_inflate_emit(const rh::InflateParams* P, void* stream);
 }
 
 using namespace rhe;
@@ -34,58 +37,62 @@ static rh_schema* plain_schema(rh_schema* s) {
   return s->plain_parent;
 }
 
-static rh_device_result* decode_blocks_impl(rh_schema* s, const uint8_t* data, uint64_t len, const uint64_t* start, const uint64_t* end,
-                                            const uint64_t* first, uint64_t nb, uint64_t num_chunks, const rh_opts* opts, rh_stats* stats) {
+// What every blocks call refuses before it looks at a block.
+static void check_blocks_call(const rh_opts* opts, const uint8_t* data, const uint64_t* start, const uint64_t* end, const uint64_t* first, uint64_t nb) {
   if (opts && opts->n_devices > 0) throw std::invalid_argument("container: a container is read on one device (rh_opts.devices is refused)");
   if (opts && (opts->flags & RH_ASYNC)) throw std::invalid_argument("container: the blocks call is synchronous: RH_ASYNC is refused");
   if (opts && opts->chunk_rows) throw std::invalid_argument("container: chunk_rows applies to rh_decode_device only");
   if (nb > 0xFFFFFFFFull) throw std::invalid_argument("container: more than 2^32 - 1 blocks");
   if (nb && (!start || !end || !data)) throw std::invalid_argument("container: null block table");
   if (!first || first[0] != 0) throw std::invalid_argument("container: first[0] must be 0");
-  rh_schema* const plain = plain_schema(s);
-  const uint64_t min_rec = plain->cs->min_record_bytes;
-  for (uint64_t b = 0; b < nb; b++) {
-    const auto where = [b] { return "container: block " + std::to_string(b) + ": "; };      // (error paths only)
-    if (start[b] > end[b] || end[b] > len || (b && start[b] < end[b - 1])) throw std::invalid_argument(where() + "its bytes are outside the buffer or out of order");
-    if (first[b + 1] < first[b]) throw std::invalid_argument(where() + "negative record count");
-    const uint64_t size = end[b] - start[b], cnt = first[b + 1] - first[b];
-    if (size >= 0xFFFFFFF0ull) throw DecodeError(where() + "a block of 4 GiB - 16 bytes or more is not supported (" + std::to_string(size) + " bytes)");
-    // what bounds a lane's loop, and through it the call's records and its offsets: every record has its minimum wire bytes
-    if (min_rec && cnt > size / min_rec)
-      throw DecodeError(where() + std::to_string(cnt) + " records cannot be in its " + std::to_string(size) + " bytes");
-  }
-  const uint64_t n = first[nb];
-  // records of no bytes at all (a schema of empty records) are bounded by no byte count: by a count for the whole call, which
-  // bounds every block's loop too -- a small file of many such blocks may not size the offsets
+}
+
+static std::string block_where(uint64_t b) { return "container: block " + std::to_string(b) + ": "; }      // (error paths only)
+
+// The checks of one block of UNCOMPRESSED bytes: its size, and what bounds a lane's loop, and through it the call's records and
+// its offsets: every record has its minimum wire bytes.
+static void check_block_size(uint64_t b, uint64_t size, uint64_t cnt, uint64_t min_rec) {
+  if (size >= 0xFFFFFFF0ull) throw DecodeError(block_where(b) + "a block of 4 GiB - 16 bytes or more is not supported (" + std::to_string(size) + " bytes)");
+  if (min_rec && cnt > size / min_rec)
+    throw DecodeError(block_where(b) + std::to_string(cnt) + " records cannot be in its " + std::to_string(size) + " bytes");
+}
+
+// records of no bytes at all (a schema of empty records) are bounded by no byte count: by a count for the whole call, which
+// bounds every block's loop too -- a small file of many such blocks may not size the offsets
+static void check_empty_records(uint64_t min_rec, uint64_t n) {
   if (!min_rec && n > kMaxEmptyRecords)
     throw DecodeError("container: " + std::to_string(n) + " records of a schema whose records may be empty: at most " +
                       std::to_string(kMaxEmptyRecords) + " in one call");
+}
 
-  require_device();
-  int device = 0;
-  if (opts && opts->device >= 0) { HIPCHK(hipSetDevice(opts->device)); device = opts->device; }
-  else HIPCHK(hipGetDevice(&device));
-  hipStream_t stream = opts ? (hipStream_t)opts->stream : nullptr;
-
-  // the file as it is (+ slack behind it), the table, the offsets, the verdict
-  Timer t_up;
-  Lease d_data(dev_pool(), len + 64, device);
-  if (len) HIPCHK(hipMemcpyAsync(d_data.ptr(), data, len, hipMemcpyHostToDevice, stream));
-  HIPCHK(hipMemsetAsync(d_data.ptr() + len, 0, 64, stream));
-  Lease d_off(dev_pool(), 8 * (n + 1), device);
-  const uint64_t o_end = 8 * nb, o_first = 16 * nb, o_err = align_up(o_first + 8 * (nb + 1), 16), o_bad = o_err + sizeof(rh::SplitErr) * nb;
-  Lease d_tab(dev_pool(), o_bad + 8, device);
-  if (nb) {
-    HIPCHK(hipMemcpyAsync(d_tab.ptr(), start, 8 * nb, hipMemcpyHostToDevice, stream));
-    HIPCHK(hipMemcpyAsync(d_tab.ptr() + o_end, end, 8 * nb, hipMemcpyHostToDevice, stream));
+// The table of a blocks call on the device: start[nb], end[nb], first[nb + 1], the split's verdicts.
+struct BlockTable {
+  Lease d_tab, d_off;
+  uint64_t o_end = 0, o_first = 0, o_err = 0, o_bad = 0;
+  void upload(const uint64_t* start, const uint64_t* end, const uint64_t* first, uint64_t nb, uint64_t n, int device, hipStream_t stream) {
+    d_off = Lease(dev_pool(), 8 * (n + 1), device);
+    o_end = 8 * nb; o_first = 16 * nb; o_err = align_up(o_first + 8 * (nb + 1), 16); o_bad = o_err + sizeof(rh::SplitErr) * nb;
+    d_tab = Lease(dev_pool(), o_bad + 8, device);
+    if (nb) {
+      HIPCHK(hipMemcpyAsync(d_tab.ptr(), start, 8 * nb, hipMemcpyHostToDevice, stream));
+      HIPCHK(hipMemcpyAsync(d_tab.ptr() + o_end, end, 8 * nb, hipMemcpyHostToDevice, stream));
+    }
+    HIPCHK(hipMemcpyAsync(d_tab.ptr() + o_first, first, 8 * (nb + 1), hipMemcpyHostToDevice, stream));
+    HIPCHK(hipMemsetAsync(d_tab.ptr() + o_err, 0, o_bad + 8 - o_err, stream));
+    if (nb == 0) HIPCHK(hipMemsetAsync(d_off.ptr(), 0, 8, stream));      // (no block, no lane: offsets[0] = 0)
   }
-  HIPCHK(hipMemcpyAsync(d_tab.ptr() + o_first, first, 8 * (nb + 1), hipMemcpyHostToDevice, stream));
-  HIPCHK(hipMemsetAsync(d_tab.ptr() + o_err, 0, o_bad + 8 - o_err, stream));
-  const uint64_t data_end = nb ? end[nb - 1] : 0;
-  if (nb == 0) HIPCHK(hipMemsetAsync(d_off.ptr(), 0, 8, stream));      // (no block, no lane: offsets[0] = 0)
-  HIPCHK(hipStreamSynchronize(stream));      // (the sources are the caller's pageable memory)
-  const float up_ms = t_up.ms();
+};
 
+// Both roads from "the table and the bytes are on the device" onward: the split launch, its verdict, the device-input decode,
+// and the result's ownership of the buffers.  d_data holds `len` bytes of uncompressed blocks at [start[b], end[b]) (+ slack).
+static rh_device_result* split_and_decode(rh_schema* s, rh_schema* plain, Lease& d_data, uint64_t len, BlockTable& T, const uint64_t* start,
+                                          const uint64_t* end, const uint64_t* first, uint64_t nb, uint64_t num_chunks, const rh_opts* opts,
+                                          rh_stats* stats, int device, hipStream_t stream, float up_ms) {
+  Lease& d_off = T.d_off;
+  Lease& d_tab = T.d_tab;
+  const uint64_t o_end = T.o_end, o_first = T.o_first, o_err = T.o_err, o_bad = T.o_bad;
+  const uint64_t n = first[nb];
+  const uint64_t data_end = nb ? end[nb - 1] : 0;
   float split_ms = 0;
   if (nb) {
     const DeviceProgram& dp = device_program(plain, device);
@@ -133,6 +140,202 @@ static rh_device_result* decode_blocks_impl(rh_schema* s, const uint8_t* data, u
   r->container_offsets = std::move(d_off);
   if (stats) stats->h2d_ms += up_ms;
   return r;
+}
+
+static rh_device_result* decode_blocks_impl(rh_schema* s, const uint8_t* data, uint64_t len, const uint64_t* start, const uint64_t* end,
+                                            const uint64_t* first, uint64_t nb, uint64_t num_chunks, const rh_opts* opts, rh_stats* stats) {
+  check_blocks_call(opts, data, start, end, first, nb);
+  rh_schema* const plain = plain_schema(s);
+  const uint64_t min_rec = plain->cs->min_record_bytes;
+  for (uint64_t b = 0; b < nb; b++) {
+    if (start[b] > end[b] || end[b] > len || (b && start[b] < end[b - 1])) throw std::invalid_argument(block_where(b) + "its bytes are outside the buffer or out of order");
+    if (first[b + 1] < first[b]) throw std::invalid_argument(block_where(b) + "negative record count");
+    check_block_size(b, end[b] - start[b], first[b + 1] - first[b], min_rec);
+  }
+  const uint64_t n = first[nb];
+  check_empty_records(min_rec, n);
+
+  require_device();
+  int device = 0;
+  if (opts && opts->device >= 0) { HIPCHK(hipSetDevice(opts->device)); device = opts->device; }
+  else HIPCHK(hipGetDevice(&device));
+  hipStream_t stream = opts ? (hipStream_t)opts->stream : nullptr;
+
+  // the file as it is (+ slack behind it), the table, the offsets, the verdict
+  Timer t_up;
+  Lease d_data(dev_pool(), len + 64, device);
+  if (len) HIPCHK(hipMemcpyAsync(d_data.ptr(), data, len, hipMemcpyHostToDevice, stream));
+  HIPCHK(hipMemsetAsync(d_data.ptr() + len, 0, 64, stream));
+  BlockTable T;
+  T.upload(start, end, first, nb, n, device, stream);
+  HIPCHK(hipStreamSynchronize(stream));      // (the sources are the caller's pageable memory)
+  const float up_ms = t_up.ms();
+  return split_and_decode(s, plain, d_data, len, T, start, end, first, nb, num_chunks, opts, stats, device, stream, up_ms);
+}
+
+// ---- deflate blocks on the device (inflate.hip) ------------------------------------------------------------------
+static_assert(sizeof(rh_inflate_status) == sizeof(rhi::Status) && sizeof(rhi::Status) == 16, "rh_inflate_status is rhi::Status");
+static_assert(RH_INFLATE_OK == rhi::ST_OK && RH_INFLATE_MALFORMED == rhi::ST_MALFORMED && RH_INFLATE_TRUNCATED == rhi::ST_TRUNCATED &&
+              RH_INFLATE_TRAILING == rhi::ST_TRAILING && RH_INFLATE_TOO_LARGE == rhi::ST_TOO_LARGE && RH_INFLATE_INTERNAL == rhi::ST_INTERNAL, "status codes");
+
+static constexpr uint64_t kBlockLimit = 0xFFFFFFF0ull;
+static std::mutex g_inflate_last_mu;
+static struct { float size_ms = 0, emit_ms = 0; uint64_t in_bytes = 0, out_bytes = 0; } g_inflate_last;
+
+// one text per rule of inflate_core.h (DESIGN.md 14 lists them)
+static const char* inflate_reason(const rhi::Status& s) {
+  static const char* const which[3] = {"code-length", "literal/length", "distance"};
+  static thread_local std::string buf;
+  switch (s.reason) {
+    case rhi::R_BLOCK_TYPE: return "block type 3";
+    case rhi::R_STORED_LEN: return "a stored block's length and its complement do not match";
+    case rhi::R_TOO_MANY: return "more than 286 literal/length or 30 distance symbols";
+    case rhi::R_REPEAT: return "a length repeat with nothing to repeat, or past the last length";
+    case rhi::R_NO_EOB: return "no code for end-of-block";
+    case rhi::R_OVERSUBSCRIBED: buf = std::string("the ") + which[s.detail < 3 ? s.detail : 0] + " code is over-subscribed"; return buf.c_str();
+    case rhi::R_INCOMPLETE: buf = std::string("the ") + which[s.detail < 3 ? s.detail : 0] + " code is incomplete"; return buf.c_str();
+    case rhi::R_NO_CODE: buf = std::string("a ") + which[s.detail < 3 ? s.detail : 0] + " symbol that has no code"; return buf.c_str();
+    case rhi::R_LITLEN_286: return "literal/length symbol 286 or 287";
+    case rhi::R_DIST_30: return "distance symbol 30 or 31";
+    case rhi::R_TOO_FAR: return "a distance further back than the bytes produced so far";
+  }
+  return "malformed stream";
+}
+
+static std::string inflate_message(uint64_t b, const rhi::Status& s) {
+  const std::string where = block_where(b) + "deflate: ";
+  switch (s.code) {
+    case rhi::ST_MALFORMED: return where + inflate_reason(s);
+    case rhi::ST_TRUNCATED: return where + "the stream ends before its final block";
+    case rhi::ST_TRAILING: return where + std::to_string(s.detail) + " bytes behind the end of the stream";
+    case rhi::ST_TOO_LARGE: return where + "it inflates to " + std::to_string(s.detail) + " bytes or more (a block of 4 GiB - 16 bytes or more is not supported)";
+  }
+  return where + "internal error";
+}
+
+// The two kernels around their one synchronisation.  size_pass: the compressed file and its table go up, sizes and verdicts come
+// back.  The caller decides what a failing block means (and sets its size to 0 if it goes on), then emit_pass leases the
+// output -- the accepted blocks back to back, no padding -- and fills it.
+struct DeviceInflate {
+  Lease d_comp, d_tab, d_out;
+  std::vector<uint64_t> size, out_start;
+  std::vector<rhi::Status> status;
+  rh::InflateParams P;
+  uint64_t nb = 0, in_bytes = 0, total = 0, o_out = 0;
+  float size_ms = 0, emit_ms = 0;
+
+  void size_pass(const uint8_t* data, uint64_t len, const uint64_t* start, const uint64_t* end, uint64_t nb_, uint64_t max_block, int device, hipStream_t stream) {
+    nb = nb_;
+    size.assign(nb, 0); out_start.assign(nb, 0); status.assign(nb, rhi::Status{0, 0, 0});
+    d_comp = Lease(dev_pool(), len + 64, device);
+    if (len) HIPCHK(hipMemcpyAsync(d_comp.ptr(), data, len, hipMemcpyHostToDevice, stream));
+    HIPCHK(hipMemsetAsync(d_comp.ptr() + len, 0, 64, stream));
+    // start[nb], end[nb], size[nb], out_start[nb], status[nb], emit_bad
+    const uint64_t o_end = 8 * nb, o_size = 16 * nb, o_st = 32 * nb, o_bad = o_st + 16 * nb;
+    o_out = 24 * nb;
+    d_tab = Lease(dev_pool(), o_bad + 8, device);
+    if (nb) {
+      HIPCHK(hipMemcpyAsync(d_tab.ptr(), start, 8 * nb, hipMemcpyHostToDevice, stream));
+      HIPCHK(hipMemcpyAsync(d_tab.ptr() + o_end, end, 8 * nb, hipMemcpyHostToDevice, stream));
+    }
+    HIPCHK(hipMemsetAsync(d_tab.ptr() + o_size, 0, o_bad + 8 - o_size, stream));
+    std::memset(&P, 0, sizeof P);
+    P.data = d_comp.ptr(); P.data_len = len;
+    P.start = (const uint64_t*)d_tab.ptr(); P.end = (const uint64_t*)(d_tab.ptr() + o_end);
+    P.nb = (uint32_t)nb; P.max_out = max_block;
+    P.size = (uint64_t*)(d_tab.ptr() + o_size); P.out_start = (const uint64_t*)(d_tab.ptr() + o_out);
+    P.status = (rhi::Status*)(d_tab.ptr() + o_st);
+    P.emit_bad = (unsigned long long*)(d_tab.ptr() + o_bad);
+    for (uint64_t b = 0; b < nb; b++) in_bytes += end[b] - start[b];
+    Events ev;
+    ev.init();
+    ev.rec(0, stream);
+    if (rh_launch_inflate_size(&P, stream)) throw HipError("k_inflate_size launch failed");
+    ev.rec(1, stream);
+    if (nb) {
+      HIPCHK(hipMemcpyAsync(size.data(), P.size, 8 * nb, hipMemcpyDeviceToHost, stream));
+      HIPCHK(hipMemcpyAsync(status.data(), P.status, 16 * nb, hipMemcpyDeviceToHost, stream));
+    }
+    HIPCHK(hipStreamSynchronize(stream));      // the one synchronisation: the host needs the total to lease the output
+    size_ms = ev.ms(0, 1);
+    for (uint64_t b = 0; b < nb; b++)
+      if (status[b].code == rhi::ST_INTERNAL) throw std::runtime_error("internal error: the inflate size kernel refused the table of block " + std::to_string(b));
+  }
+
+  void emit_pass(int device, hipStream_t stream) {
+    total = 0;
+    for (uint64_t b = 0; b < nb; b++) {
+      if (status[b].code != rhi::ST_OK) size[b] = 0;
+      out_start[b] = total;
+      total += size[b];
+    }
+    d_out = Lease(dev_pool(), total + 64, device);
+    HIPCHK(hipMemsetAsync(d_out.ptr() + total, 0, 64, stream));
+    if (nb) HIPCHK(hipMemcpyAsync(d_tab.ptr() + o_out, out_start.data(), 8 * nb, hipMemcpyHostToDevice, stream));
+    P.out = d_out.ptr(); P.out_len = total;
+    Events ev;
+    ev.init();
+    ev.rec(0, stream);
+    if (rh_launch_inflate_emit(&P, stream)) throw HipError("k_inflate_emit launch failed");
+    ev.rec(1, stream);
+    unsigned long long bad = 0;
+    HIPCHK(hipMemcpyAsync(&bad, P.emit_bad, 8, hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipStreamSynchronize(stream));
+    emit_ms = ev.ms(0, 1);
+    if (bad) throw std::runtime_error("internal error: the emit walk of deflate block " + std::to_string(~bad) + " disagrees with its size pass");
+    d_comp.release();
+    std::lock_guard<std::mutex> g(g_inflate_last_mu);
+    g_inflate_last.size_ms = size_ms; g_inflate_last.emit_ms = emit_ms; g_inflate_last.in_bytes = in_bytes; g_inflate_last.out_bytes = total;
+  }
+};
+
+static uint64_t block_limit_of(uint64_t max_block_bytes) { return max_block_bytes && max_block_bytes < kBlockLimit ? max_block_bytes : kBlockLimit; }
+
+static void check_compressed_table(const uint64_t* start, const uint64_t* end, uint64_t nb, uint64_t len) {
+  for (uint64_t b = 0; b < nb; b++)
+    if (start[b] > end[b] || end[b] > len || (b && start[b] < end[b - 1])) throw std::invalid_argument(block_where(b) + "its bytes are outside the buffer or out of order");
+}
+
+static rh_device_result* decode_cblocks_impl(rh_schema* s, const uint8_t* data, uint64_t len, const uint64_t* start, const uint64_t* end,
+                                             const uint64_t* first, uint64_t nb, int codec, uint64_t max_block_bytes, uint64_t num_chunks,
+                                             const rh_opts* opts, rh_stats* stats) {
+  if (codec == RH_CODEC_NULL) return decode_blocks_impl(s, data, len, start, end, first, nb, num_chunks, opts, stats);
+  if (codec != RH_CODEC_DEFLATE) throw std::invalid_argument("container: codec must be RH_CODEC_NULL or RH_CODEC_DEFLATE");
+  check_blocks_call(opts, data, start, end, first, nb);
+  rh_schema* const plain = plain_schema(s);
+  const uint64_t min_rec = plain->cs->min_record_bytes;
+  check_compressed_table(start, end, nb, len);
+  for (uint64_t b = 0; b < nb; b++)
+    if (first[b + 1] < first[b]) throw std::invalid_argument(block_where(b) + "negative record count");
+  const uint64_t n = first[nb];
+  check_empty_records(min_rec, n);
+
+  require_device();
+  int device = 0;
+  if (opts && opts->device >= 0) { HIPCHK(hipSetDevice(opts->device)); device = opts->device; }
+  else HIPCHK(hipGetDevice(&device));
+  hipStream_t stream = opts ? (hipStream_t)opts->stream : nullptr;
+
+  Timer t_up;
+  DeviceInflate I;
+  I.size_pass(data, len, start, end, nb, block_limit_of(max_block_bytes), device, stream);
+  // deflate failures come before any record is walked, the lowest block first: as on the host road, which inflates every block first
+  for (uint64_t b = 0; b < nb; b++)
+    if (I.status[b].code != rhi::ST_OK) throw DecodeError(inflate_message(b, I.status[b]));
+  std::vector<uint64_t> istart(nb), iend(nb);
+  uint64_t at = 0;
+  for (uint64_t b = 0; b < nb; b++) {
+    check_block_size(b, I.size[b], first[b + 1] - first[b], min_rec);
+    istart[b] = at;
+    at += I.size[b];
+    iend[b] = at;
+  }
+  I.emit_pass(device, stream);
+  BlockTable T;
+  T.upload(istart.data(), iend.data(), first, nb, n, device, stream);
+  HIPCHK(hipStreamSynchronize(stream));      // (istart / iend are this frame's)
+  const float up_ms = t_up.ms() - I.size_ms - I.emit_ms;
+  return split_and_decode(s, plain, I.d_out, I.total, T, istart.data(), iend.data(), first, nb, num_chunks, opts, stats, device, stream, up_ms);
 }
 
 }  // namespace rhe
@@ -214,6 +417,84 @@ int rh_decode_blocks(const rh_schema* s, const uint8_t* data, uint64_t len, cons
     if (stats) stats->total_ms = t.ms();
     return rc;
   });
+}
+
+int rh_decode_cblocks_device(const rh_schema* s, const uint8_t* data, uint64_t len, const uint64_t* start, const uint64_t* end,
+                             const uint64_t* first, uint64_t nb, int codec, uint64_t max_block_bytes, uint64_t num_chunks,
+                             const rh_opts* opts, rh_device_result** out, rh_stats* stats, char** err) {
+  if (!s || !out) return RH_ERR_ARGUMENT;
+  *out = nullptr;
+  return guarded(err, [&] {
+    Timer t;
+    rh_opts pub;
+    if (opts) { pub = *opts; pub.flags &= kPublicFlags; }
+    *out = decode_cblocks_impl(const_cast<rh_schema*>(s), data, len, start, end, first, nb, codec, max_block_bytes, num_chunks,
+                               opts ? &pub : nullptr, stats);
+    if (stats) stats->total_ms = t.ms();
+    return RH_OK;
+  });
+}
+
+int rh_decode_cblocks(const rh_schema* s, const uint8_t* data, uint64_t len, const uint64_t* start, const uint64_t* end,
+                      const uint64_t* first, uint64_t nb, int codec, uint64_t max_block_bytes, uint64_t num_chunks, const rh_opts* opts,
+                      struct ArrowArray* out_chunks, uint32_t* out_k, rh_stats* stats, char** err) {
+  if (!s || !out_chunks) return RH_ERR_ARGUMENT;
+  return guarded(err, [&] {
+    Timer t;
+    rh_opts pub;
+    if (opts) { pub = *opts; pub.flags &= kPublicFlags; }
+    std::unique_ptr<rh_device_result> r(decode_cblocks_impl(const_cast<rh_schema*>(s), data, len, start, end, first, nb, codec, max_block_bytes,
+                                                            num_chunks, opts ? &pub : nullptr, stats));
+    Timer td;
+    const int rc = to_host_impl(r.get(), out_chunks, opts ? (hipStream_t)opts->stream : nullptr);
+    if (stats) stats->d2h_ms = td.ms();
+    if (out_k) *out_k = r->k;
+    if (stats) stats->total_ms = t.ms();
+    return rc;
+  });
+}
+
+int rh_inflate_blocks(const uint8_t* data, uint64_t len, const uint64_t* start, const uint64_t* end, uint64_t nb, uint64_t max_block_bytes,
+                      const rh_opts* opts, uint8_t** out, uint64_t* out_len, uint64_t* out_start, uint64_t* out_end,
+                      rh_inflate_status* status, char** err) {
+  if (!out || !out_len || (nb && (!out_start || !out_end || !status))) return RH_ERR_ARGUMENT;
+  *out = nullptr;
+  *out_len = 0;
+  return guarded(err, [&] {
+    if (opts && opts->n_devices > 0) throw std::invalid_argument("container: a container is read on one device (rh_opts.devices is refused)");
+    if (opts && (opts->flags & RH_ASYNC)) throw std::invalid_argument("container: the blocks call is synchronous: RH_ASYNC is refused");
+    if (nb > 0xFFFFFFFFull) throw std::invalid_argument("container: more than 2^32 - 1 blocks");
+    if (nb && (!start || !end || !data)) throw std::invalid_argument("container: null block table");
+    check_compressed_table(start, end, nb, len);
+    require_device();
+    int device = 0;
+    if (opts && opts->device >= 0) { HIPCHK(hipSetDevice(opts->device)); device = opts->device; }
+    else HIPCHK(hipGetDevice(&device));
+    hipStream_t stream = opts ? (hipStream_t)opts->stream : nullptr;
+    DeviceInflate I;
+    I.size_pass(data, len, start, end, nb, block_limit_of(max_block_bytes), device, stream);
+    I.emit_pass(device, stream);      // (a failing block contributes no byte)
+    std::unique_ptr<uint8_t, void (*)(void*)> host((uint8_t*)std::malloc(I.total ? I.total : 1), std::free);
+    if (!host) throw std::bad_alloc();
+    if (I.total) HIPCHK(hipMemcpyAsync(host.get(), I.d_out.ptr(), I.total, hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipStreamSynchronize(stream));
+    for (uint64_t b = 0; b < nb; b++) {
+      out_start[b] = I.out_start[b];
+      out_end[b] = I.out_start[b] + I.size[b];
+      status[b].code = I.status[b].code; status[b].reason = I.status[b].reason; status[b].detail = I.status[b].detail;
+    }
+    *out = host.release();
+    *out_len = I.total;
+    return RH_OK;
+  });
+}
+
+void rh_inflate_last(float* size_ms, float* emit_ms, uint64_t* in_bytes, uint64_t* out_bytes) {
+  std::lock_guard<std::mutex> g(g_inflate_last_mu);
+  if (size_ms) *size_ms = g_inflate_last.size_ms;
+  if (emit_ms) *emit_ms = g_inflate_last.emit_ms;
+  if (in_bytes) *in_bytes = g_inflate_last.in_bytes;
+  if (out_bytes) *out_bytes = g_inflate_last.out_bytes;
 }
 
 }  // extern "C"

@@ -11,6 +11,9 @@
 Every figure is the median of `--reps` calls: end-to-end wall time, and for the container reads the split kernel's own GPU time
 (rh_split_last_ms) next to the decode kernels' (size, scan, emit: rh_stats), and the host's share of one blocks call: inflating,
 the upload of the file (rh_stats.h2d_ms) and the export of the results to host memory (d2h_ms).  No threshold: the table prices the split walk.
+`--inflate` measures instead the two roads of a `deflate` file ("Deflate blocks on the device"): the same records at
+~64 KB and ~1 MB blocks, read_container(inflate="host") and (inflate="device") alternated in one job, medians of 3, with the two
+inflate kernels' GPU times (rh_inflate_last) and the split's beside them -> profiles/container_inflate_10m.json.
 One JSON object on stdout, also written to --out; the Markdown table on stderr and into DESIGN.md 14, between its two marker
 lines (--design '' leaves the document alone; --from-json FILE rewrites the table from an earlier run's JSON without measuring).
 """
@@ -90,14 +93,87 @@ def report(out: dict, design: str) -> None:
         open(design, "w").write(text[:i] + "\n" + t + "\n" + text[j:])
 
 
+def inflate_rows(a) -> int:
+    """The two roads of a deflate container, alternated: the yardstick is the host row of the same job."""
+    import numpy as np
+    import torch  # noqa: F401  first: the engine shares torch's HIP runtime
+    from avrogen import fastgen
+    from avrogen.schemas import SCHEMAS
+    import pyruhvro_amd as P
+    from pyruhvro_amd import cabi
+
+    t_start = time.perf_counter()
+
+    def note(what):
+        print(f"[{time.perf_counter() - t_start:6.1f} s] {what}", file=sys.stderr, flush=True)
+
+    schema = SCHEMAS["full"]
+    note(f"generating {a.records} records")
+    data, offsets = fastgen.generate("full", a.records)
+    reps = 3
+    out = {"workload": "full", "records": a.records, "payload_bytes": int(offsets[-1]), "chunks": 8, "reps": reps, "codec": "deflate", "rows": {}}
+    old = P.set_kernel_mode("specialized")
+    for label, block_bytes in (("deflate_64k", 64 << 10), ("deflate_1m", 1 << 20)):
+        note(f"{label}: deflating")
+        blob, nb = container_of(schema, data, offsets, block_bytes, "deflate")
+        note(f"{label}: {nb} blocks, {len(blob)} bytes")
+        walls = {"host": [], "device": []}
+        kern = []
+        first = {}
+        for rep in range(-1, reps):      # (rep -1: both roads once, warm, and compared)
+            for road in ("host", "device"):
+                t0 = time.perf_counter()
+                b = P.read_container(blob, 8, inflate=road)
+                ms = (time.perf_counter() - t0) * 1e3
+                note(f"{label}: {road} {ms:.0f} ms")
+                if rep < 0:
+                    first[road] = b
+                    continue
+                del b
+                walls[road].append(ms)
+                if road == "device":
+                    kern.append(dict(cabi.inflate_last(), split_ms=cabi.split_last_ms()))
+                else:
+                    kern.append({"host_split_ms": cabi.split_last_ms()})
+            if rep < 0:
+                assert all(x.equals(y) for x, y in zip(first["host"], first["device"])) and len(first["host"]) == len(first["device"])
+                first.clear()
+        row = {"blocks": nb, "file_bytes": len(blob)}
+        for road in ("host", "device"):
+            w = walls[road]
+            row[road] = {"wall_ms": statistics.median(w), "wall_ms_min": min(w), "wall_ms_max": max(w)}
+        dev = [k for k in kern if "size_ms" in k]
+        row["host"]["split_ms"] = statistics.median(k["host_split_ms"] for k in kern if "host_split_ms" in k)
+        row["device"].update({"inflate_size_kernel_ms": statistics.median(k["size_ms"] for k in dev),
+                              "inflate_emit_kernel_ms": statistics.median(k["emit_ms"] for k in dev),
+                              "split_ms": statistics.median(k["split_ms"] for k in dev),
+                              "in_bytes": dev[0]["in_bytes"], "out_bytes": dev[0]["out_bytes"]})
+        row["device_over_host"] = row["device"]["wall_ms"] / row["host"]["wall_ms"]
+        out["rows"][label] = row
+        del blob
+    P.set_kernel_mode(old)
+    note("done")
+    text = json.dumps(out, indent=1)
+    print(text)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        open(a.out, "w").write(text + "\n")
+    return 0
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--inflate", action="store_true", help="the host and the device road of a deflate file (see above); --out defaults to profiles/container_inflate_10m.json")
     ap.add_argument("--design", default=os.path.join(ROOT, "DESIGN.md"), help="the document whose table is rewritten ('' = none)")
     ap.add_argument("--from-json", default=None, help="no measurement: the table of an earlier run's JSON")
     ap.add_argument("--records", type=int, default=10_000_000)
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "container_full10m.json"))
     a = ap.parse_args()
+    if a.inflate:
+        if a.out == ap.get_default("out"):
+            a.out = os.path.join(ROOT, "profiles", "container_inflate_10m.json")
+        return inflate_rows(a)
     if a.from_json:
         report(json.load(open(a.from_json)), a.design)
         return 0
