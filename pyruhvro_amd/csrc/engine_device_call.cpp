@@ -4,6 +4,45 @@
 
 using namespace rhe;
 
+// The head of a control block handed to a pinned host block behind a token: rh_k_publish copies the head words (and the summed
+// null counts), leaves the device block zeroed and stores the token last.  The host spins on that word: this call only (later
+// calls stay queued behind it), no event in the stream, and sooner than a stream wait returns.  The main call and the lean
+// probe both hand over this way.
+struct Handover {
+  void* hdev = nullptr;              // the host block as the device sees it
+  volatile uint32_t* flag = nullptr;
+  uint32_t token = 0;
+  enum Seen { TOKEN, DONE_WITHOUT, FAILED };
+  // Can a kernel write this pinned block?  (Asked before anything of the hand-over is launched: the caller keeps its fall-back.)
+  bool map(uint8_t* host) {
+    if (hipHostGetDevicePointer(&hdev, host, 0) == hipSuccess && hdev) return true;
+    (void)hipGetLastError();
+    return false;
+  }
+  // rh_launch_publish's status: head_words of the block at d_ctrl, null_entries summed counts behind them, the token at flag_off
+  int publish(uint8_t* d_ctrl, uint8_t* host, uint32_t head_words, uint32_t null_entries, uint64_t flag_off, uint32_t null_slots, hipStream_t stream) {
+    static std::atomic<uint32_t> next_token{1};      // one counter for the process; a token is never 0 (the cleared flag word)
+    do token = next_token.fetch_add(1); while (token == 0);
+    flag = (volatile uint32_t*)(host + flag_off);
+    *flag = 0;
+    return rh_launch_publish(d_ctrl, hdev, head_words, null_entries, (uint32_t)(flag_off / 4), token, null_slots, stream);
+  }
+  Seen wait(hipStream_t stream, hipError_t* why = nullptr) const {
+    for (uint32_t spins = 0; __atomic_load_n(flag, __ATOMIC_ACQUIRE) != token;) {
+      if ((++spins & 0xFFFFu) == 0) {              // a failed launch or a fault must not hang the caller
+        const hipError_t q = hipStreamQuery(stream);
+        // everything on the stream is done: the token is there or never will be
+        if (q == hipSuccess) return __atomic_load_n(flag, __ATOMIC_ACQUIRE) == token ? TOKEN : DONE_WITHOUT;
+        if (q != hipErrorNotReady) { if (why) *why = q; return FAILED; }
+      }
+#if defined(__x86_64__)
+      __builtin_ia32_pause();
+#endif
+    }
+    return TOKEN;
+  }
+};
+
 // One device-resident decode call.  enqueue() puts the whole call on the stream (k_size -> k_scan+k_layout -> k_init ->
 // k_emit -> one D2H of the control words) and finish() waits for it and settles the result (error check, arena
 // retry, host tables).  rh_decode_device runs both back to back; with RH_ASYNC the result is handed out between the
@@ -22,55 +61,56 @@ struct rh_decode_call {
   rh_stats st;
   rh_device_result& r;
   HostProf hp;
+  bool range_of_host_call = false;   // a chunk range of a host call (decode_range) or a group of a split call: the caller gave the geometry
+  bool async = false;           // RH_ASYNC: the call is settled later; without rh_k_publish its end is marked with a DoneEvent
+  // in-call overlap (decode_device_split, staggered form): this group's size pass starts behind `start_after` (the previous
+  // group's size pass) and marks its own end with `sized`, so that size pass g+1 runs beside emit pass g
+  hipEvent_t start_after = nullptr, sized = nullptr;
+  // geometry (chunk_geometry; the tiles follow from the kernel form: choose_kernels)
   int device = 0;
   hipStream_t stream = nullptr;
   ChunkGeo geo_v;
   const ChunkGeo* geo = nullptr;
-  // derived
-  uint32_t k = 1;
+  uint32_t k = 1, nblocks = 0;
   int K = 0, nnodes = 0, nbuf = 0;
   const DeviceProgram* dp = nullptr;
+  uint64_t narrow_rows = 0, tile = 0, bpc64 = 0, payload = 0;
+  // kernel choice (choose_kernels, lean_select)
   const SpecKernel* sk = nullptr;
   hipFunction_t size_r = nullptr, emit_r = nullptr;     // the ranged pair, when this call launches it (tiles past the LDS window)
   // The pair the two-pass form launches: the schema's default (wide) rh_spec_size / rh_spec_emit, or its lean pair (lean_select)
   hipFunction_t size_f = nullptr, emit_f = nullptr;
   hipFunction_t lean_size = nullptr, lean_emit = nullptr;      // the lean pair, loaded, when this call qualifies for it
   bool lean = false;            // ... and launches it
-  // the probe (launch_probe): the lean size kernel over a sample of this call's tiles, on a workspace and control block of its own
-  bool probing = false;
-  uint32_t probe_token = 0;
-  Lease probe_ws, probe_host;
-  std::unique_ptr<CtrlLease> probe_ctrl;
-  uint64_t narrow_rows = 0, tile = 0, bpc64 = 0, payload = 0;
-  uint32_t nblocks = 0;
-  uint64_t o_null = 0, o_tot = 48, ctrl_bytes = 0;
-  uint32_t null_slots = rh::kNullSlots;      // program.h null_slots_for(k)
+  // control block, workspace, tables (place_blocks)
+  CtrlPlan cp;
   Lease ws, hctrl, dtab, prof_buf;
   std::unique_ptr<CtrlLease> ctrl;
   rh::KParams P;
-  uint32_t lds_bytes = 0, emit_lds = 0;
-  bool profile = false;
-  Events ev;
-  std::vector<uint64_t> totals;
   uint64_t n_entries = 0, tab_bytes = 0;
   uint64_t* d_sizes = nullptr;
+  bool child_bitmaps = false, size_pass = false;
+  // window (set_window)
+  uint32_t lds_bytes = 0;
+  // the submission (try_single / submit_two_pass) and its settlement (finish)
+  Events ev;
+  std::vector<uint64_t> totals;
   uint64_t exact = 0;
-  bool child_bitmaps = false, fused = false, timed_size = false;
-  bool range_of_host_call = false;   // a chunk range of a host call (decode_range) or a group of a split call: the caller gave the geometry
+  bool fused = false, timed_size = false;
   bool single = false;          // the single-pass form ran (rh_spec_fused): arena laid out from capacities
   std::vector<uint64_t> caps;   // [K][k] those capacities
-  uint64_t arena_cap = 0, o_tick = 0;
+  uint64_t arena_cap = 0;
   Lease lookback, hcaps;
   double basis = 0;
-  bool settled = false;         // finish() ran (or the call completed inside enqueue())
-  bool async = false;           // RH_ASYNC: the call is settled later; without rh_k_publish its end is marked with a DoneEvent
-  DoneEvent done;
-  // in-call overlap (decode_device_split, staggered form): this group's size pass starts behind `start_after` (the previous
-  // group's size pass) and marks its own end with `sized`, so that size pass g+1 runs beside emit pass g
-  hipEvent_t start_after = nullptr, sized = nullptr;
   bool published = false;       // rh_k_publish ran: hctrl holds the compact layout (summed null counts) behind a token
-  uint32_t token = 0;
-  uint64_t o_flag_h = 0;
+  Handover head;
+  DoneEvent done;
+  bool settled = false;         // finish() ran (or the call completed inside enqueue())
+  // the probe (launch_probe): the lean size kernel over a sample of this call's tiles, on a workspace and control block of its own
+  bool probing = false;
+  Handover probe_head;
+  Lease probe_ws, probe_host;
+  std::unique_ptr<CtrlLease> probe_ctrl;
 
   rh_decode_call(rh_schema* s_, const uint8_t* data, const uint64_t* offs, uint64_t dl, uint64_t n_, uint64_t nc, const rh_opts* o,
                bool stats, const ChunkGeo* g, rh_device_result& res)
@@ -118,10 +158,48 @@ struct rh_decode_call {
   // next calls to launch the ranged pair.  hctrl holds the head of the control block as the call's last emit pass left it.
   void learn_unsized_tiles() {
     if (timed_size || single || n == 0) return;
-    const uint32_t* stw = (const uint32_t*)(hctrl.ptr() + 32);
+    const uint32_t* stw = tile_stats();
     count(RH_CTR_OVER_WINDOW_TILES, stw[1]); count(RH_CTR_SUBTILED_TILES, stw[3]);
-    if (stw[1]) s->ranged_calls.store(kRangedKeep, std::memory_order_relaxed);
-    else { uint32_t v = s->ranged_calls.load(std::memory_order_relaxed); if (v) s->ranged_calls.compare_exchange_weak(v, v - 1, std::memory_order_relaxed); }
+    ranged_learn(stw[1] != 0);
+  }
+
+  // The tile statistics of the call, control words 8..11 as hctrl holds them: careful tiles, tiles past the window, re-walked
+  // wavefronts, tiles walked in ranges
+  const uint32_t* tile_stats() const { return (const uint32_t*)(hctrl.ptr() + 32); }
+
+  // Tiles past the window: this schema's next kRangedKeep calls launch the ranged pair (and compile it if need be); a call that
+  // met none counts that down
+  void ranged_learn(bool met) {
+    if (met) { s->ranged_calls.store(kRangedKeep, std::memory_order_relaxed); return; }
+    uint32_t v = s->ranged_calls.load(std::memory_order_relaxed);
+    if (v) s->ranged_calls.compare_exchange_weak(v, v - 1, std::memory_order_relaxed);
+  }
+
+  // program.h LParams of this call's arena layout: from the device's totals (narrow: the specialised kernels' 32-bit bounds are
+  // checked) or from the single-pass form's capacities
+  rh::LParams layout_params(uint64_t* col_totals, bool narrow) const {
+    rh::LParams LP;
+    std::memset(&LP, 0, sizeof LP);
+    LP.totals = col_totals; LP.desc = dp->desc; LP.sz = r.sz; LP.rows_last = r.rows_last; LP.n = n; LP.k = k;
+    LP.nbuf = nbuf; LP.K = K; LP.ndom = cs.ndom; LP.arena = r.arena.ptr(); LP.capacity = r.arena.b.size;
+    LP.bufptr = (void**)dtab.ptr(); LP.bufsize = d_sizes; LP.ctrl = P.first_bad; LP.narrow = narrow ? 1u : 0u;
+    LP.narrow_rows = narrow_rows;
+    return LP;
+  }
+
+  // The call's last launch: the head of the control block goes to hctrl behind a token (Handover), which also leaves the block
+  // zeroed for its next user -- or, where a kernel cannot write hctrl (or RUHVRO_HIP_NO_PUBLISH=1), one D2H copy of the block
+  // and, for an asynchronous call, an event behind it.
+  void publish_head(bool allowed) {
+    if (allowed && head.map(hctrl.ptr())) {
+      if (head.publish(ctrl->ptr(), hctrl.ptr(), (uint32_t)(cp.o_null / 4), (uint32_t)(nnodes * (int)k), cp.o_flag_h, cp.null_slots, stream))
+        throw HipError("k_publish launch failed");
+      ctrl->b.clean = true;
+      published = true;
+    } else {
+      HIPCHK(hipMemcpyAsync(hctrl.ptr(), ctrl->ptr(), cp.bytes, hipMemcpyDeviceToHost, stream));
+      if (async) done.record(device, stream);
+    }
   }
 
   // host statement of the layout (same rule, same table order as rh_k_layout): fills the result's tables
@@ -147,11 +225,10 @@ struct rh_decode_call {
     if (nbuf > 0 && (child_bitmaps || !offsets_done) &&
         rh_launch_init(P.bufptr, d_sizes, dp->desc, (uint32_t)nbuf, k, P.first_bad, stream)) throw HipError("k_init launch failed");
     if (n > 0) {
-      emit_lds = lds_bytes;
-      if (sk ? launch_module(emit_f, P, nblocks, (uint32_t)tile, emit_lds, stream, ev.at(3), P.ranged ? nullptr : ev.at(4))
-             : (cs.projected ? rh_launch_emit_drop : rh_launch_emit)(&P, emit_lds, stream, ev.at(3), ev.at(4)))
+      if (sk ? launch_module(emit_f, P, nblocks, (uint32_t)tile, lds_bytes, stream, ev.at(3), P.ranged ? nullptr : ev.at(4))
+             : (cs.projected ? rh_launch_emit_drop : rh_launch_emit)(&P, lds_bytes, stream, ev.at(3), ev.at(4)))
         throw HipError("k_emit launch failed");
-      if (P.ranged && launch_module(emit_r, P, nblocks + (P.worklist ? rh::kBigFront : 0u), (uint32_t)tile, emit_lds, stream, nullptr, ev.at(4))) throw HipError("k_emit (ranged) launch failed");
+      if (P.ranged && launch_module(emit_r, P, nblocks + (P.worklist ? rh::kBigFront : 0u), (uint32_t)tile, lds_bytes, stream, nullptr, ev.at(4))) throw HipError("k_emit (ranged) launch failed");
     } else {
       ev.rec(3, stream);
       ev.rec(4, stream);
@@ -175,8 +252,8 @@ struct rh_decode_call {
     HIPCHK(hipMemsetAsync(ctrl->ptr() + 8, 0, 8, stream));    // clear the layout flag (and the ticket) of a refused optimistic attempt
     launch_tail(false);
     // (not the totals: the host has them, and rh_k_publish may have zeroed the device copy of a refused attempt)
-    HIPCHK(hipMemcpyAsync(hctrl.ptr(), ctrl->ptr(), o_tot, hipMemcpyDeviceToHost, stream));
-    HIPCHK(hipMemcpyAsync(hctrl.ptr() + o_null, ctrl->ptr() + o_null, ctrl_bytes - o_null, hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipMemcpyAsync(hctrl.ptr(), ctrl->ptr(), cp.o_tot, hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipMemcpyAsync(hctrl.ptr() + cp.o_null, ctrl->ptr() + cp.o_null, cp.bytes - cp.o_null, hipMemcpyDeviceToHost, stream));
     HIPCHK(hipStreamSynchronize(stream));      // also keeps htab alive until the table copy is done
     check_bad(hctrl.ptr());
   }
@@ -237,10 +314,8 @@ struct rh_decode_call {
     const uint64_t q_end = align_up(q_lcnt + 4ull * (uint64_t)((cs.KL + 1) / 2) * pn * tile, kAlign) + kAlign;
     probe_ws = Lease(dev_pool(), q_end, device);
     probe_host = Lease(pin_pool(), 256, device);
-    probe_ctrl.reset(new CtrlLease(ctrl_bytes, device, stream));      // all zero; zeroed again on its way back (CtrlPool)
-    void* hdev = nullptr;
-    if (hipHostGetDevicePointer(&hdev, probe_host.ptr(), 0) != hipSuccess || !hdev) {
-      (void)hipGetLastError();
+    probe_ctrl.reset(new CtrlLease(cp.bytes, device, stream));      // all zero; zeroed again on its way back (CtrlPool)
+    if (!probe_head.map(probe_host.ptr())) {
       probe_abandon();
       return;
     }
@@ -248,22 +323,19 @@ struct rh_decode_call {
     Q.k = kp; Q.rows_last = rows_lastp; Q.bpc = per; Q.nblocks = pn;
     Q.ranged = 0; Q.worklist = nullptr; Q.bigmark = nullptr; Q.all_careful = 0; Q.lookback = nullptr; Q.caps = nullptr;
     Q.first_bad = (unsigned long long*)probe_ctrl->ptr();
-    Q.nullcount = (uint32_t*)(probe_ctrl->ptr() + o_null);
-    Q.totals = (uint64_t*)(probe_ctrl->ptr() + o_tot);
-    Q.tickets = (uint32_t*)(probe_ctrl->ptr() + o_tick);
+    Q.nullcount = (uint32_t*)(probe_ctrl->ptr() + cp.o_null);
+    Q.totals = (uint64_t*)(probe_ctrl->ptr() + cp.o_tot);
+    Q.tickets = (uint32_t*)(probe_ctrl->ptr() + cp.o_tick);
     Q.errinfo = (rh::ErrInfo*)probe_ws.ptr();
     Q.blocksum = (uint32_t*)(probe_ws.ptr() + q_bsum);
     Q.blockbase = Q.blocksum;                              // (not read by the size kernel)
     Q.tileflag = (uint32_t*)(probe_ws.ptr() + q_flag);
     Q.lanecnt = (uint32_t*)(probe_ws.ptr() + q_lcnt);
     Q.lanecnt32 = nullptr;
-    static std::atomic<uint32_t> next_token{0x20000001u};
-    probe_token = next_token.fetch_add(1);
-    if (probe_token == 0) probe_token = next_token.fetch_add(1);
-    *(volatile uint32_t*)(probe_host.ptr() + 48) = 0;
+    // (the probe's head: the twelve control words, no null counts, the token behind them)
     if (launch_module(lean_size, Q, pn, (uint32_t)tile, lds_bytes, stream) ||
         rh_launch_tile_stats(probe_ctrl->ptr(), Q.tileflag, pn, stream) ||
-        rh_launch_publish(probe_ctrl->ptr(), hdev, 12, 0, 12, probe_token, null_slots, stream))
+        probe_head.publish(probe_ctrl->ptr(), probe_host.ptr(), 12, 0, 48, cp.null_slots, stream))
       throw HipError("lean probe launch failed");
   }
 
@@ -279,16 +351,7 @@ struct rh_decode_call {
   // else: wide, and the next probe comes 64 qualifying calls later.
   void probe_settle() {
     if (!probing) return;
-    volatile uint32_t* flag = (volatile uint32_t*)(probe_host.ptr() + 48);
-    bool got = true;
-    for (uint32_t spins = 0; __atomic_load_n(flag, __ATOMIC_ACQUIRE) != probe_token;) {
-      if ((++spins & 0xFFFFu) == 0) {
-        const hipError_t q = hipStreamQuery(stream);
-        if (q == hipErrorNotReady) continue;
-        got = __atomic_load_n(flag, __ATOMIC_ACQUIRE) == probe_token;      // the stream is done (or failed): the token is there or never will be
-        break;
-      }
-    }
+    const bool got = probe_head.wait(stream) == Handover::TOKEN;      // (a stream that ended without it, or failed: not clean)
     const uint32_t* h = (const uint32_t*)probe_host.ptr();
     const bool clean = got && h[0] == 0 && h[1] == 0 && h[2] == 0 && h[8] == 0 && h[9] == 0 && h[10] == 0;
     lean_count(LC_PROBES);
@@ -386,41 +449,21 @@ struct rh_decode_call {
     HIPCHK(hipMemcpyAsync(d_caps, hcaps.ptr(), 8ull * K * k, hipMemcpyHostToDevice, stream));
     P.lookback = (unsigned long long*)lookback.ptr();
     P.caps = d_caps;
-    rh::LParams LP;
-    std::memset(&LP, 0, sizeof LP);
-    LP.totals = d_caps; LP.desc = dp->desc; LP.sz = r.sz; LP.rows_last = r.rows_last; LP.n = n; LP.k = k;
-    LP.nbuf = nbuf; LP.K = K; LP.ndom = cs.ndom; LP.arena = r.arena.ptr(); LP.capacity = r.arena.b.size;
-    LP.bufptr = (void**)dtab.ptr(); LP.bufsize = d_sizes; LP.ctrl = P.first_bad; LP.narrow = 0;
-    LP.narrow_rows = narrow_rows;
+    const rh::LParams LP = layout_params(d_caps, false);
     if (rh_launch_layout(&LP, stream)) throw HipError("k_layout launch failed");
     if (nbuf > 0 && child_bitmaps && rh_launch_init(P.bufptr, d_sizes, dp->desc, (uint32_t)nbuf, k, P.first_bad, stream))
       throw HipError("k_init launch failed");
     const uint64_t tiles_max = std::max<uint64_t>((r.sz + tile - 1) / tile, (r.rows_last + tile - 1) / tile);
-    emit_lds = lds_bytes;
-    if (launch_module(fused_fn, P, (uint32_t)(tiles_max * k), (uint32_t)tile, emit_lds, stream, ev.at(3), ev.at(4)))
+    if (launch_module(fused_fn, P, (uint32_t)(tiles_max * k), (uint32_t)tile, lds_bytes, stream, ev.at(3), ev.at(4)))
       throw HipError("k_fused launch failed");
     basis = (double)payload + 64.0 * (double)n;
-    void* hdev = nullptr;
-    if (hipHostGetDevicePointer(&hdev, hctrl.ptr(), 0) == hipSuccess && hdev) {
-      static std::atomic<uint32_t> next_token{0x40000001u};
-      token = next_token.fetch_add(1);
-      if (token == 0) token = next_token.fetch_add(1);
-      o_flag_h = align_up(o_null + 4ull * nnodes * k, 8);
-      *(volatile uint32_t*)(hctrl.ptr() + o_flag_h) = 0;
-      if (rh_launch_publish(ctrl->ptr(), hdev, (uint32_t)(o_null / 4), (uint32_t)(nnodes * (int)k), (uint32_t)(o_flag_h / 4), token, null_slots, stream))
-        throw HipError("k_publish launch failed");
-      ctrl->b.clean = true;
-      published = true;
-    } else {
-      (void)hipGetLastError();
-      HIPCHK(hipMemcpyAsync(hctrl.ptr(), ctrl->ptr(), ctrl_bytes, hipMemcpyDeviceToHost, stream));
-      if (async) done.record(device, stream);
-    }
+    publish_head(true);
     return true;
   }
 
-  void enqueue() {
-    Range rk("ruhvro_hip:decode_device (k_size, k_scan, k_layout, k_init, k_emit)");
+  // ---- enqueue(), step by step ----
+  // 1. device, stream and the chunks: k chunks of sz rows, the last one rows_last
+  void chunk_geometry() {
     if (opts.device >= 0) { HIPCHK(hipSetDevice(opts.device)); device = opts.device; }
     else HIPCHK(hipGetDevice(&device));
     stream = (hipStream_t)opts.stream;
@@ -436,16 +479,11 @@ struct rh_decode_call {
       }
     }
 
-    r.cs = &cs;
-    r.device = device;
-    r.n = n;
+    r.cs = &cs; r.device = device; r.n = n;
     if (!geo && opts.chunk_rows) {   // a range of a larger call's chunks (one process per GPU): rh_opts.chunk_rows
-      if (num_chunks < 1 || num_chunks > 0xFFFFFFFFull || (num_chunks - 1) > n / opts.chunk_rows ||
-          (n > 0 && n == (num_chunks - 1) * opts.chunk_rows && num_chunks > 1))
+      if (!explicit_geometry_ok(n, num_chunks, opts.chunk_rows))
         throw std::invalid_argument("chunk_rows: the n records do not make num_chunks chunks of chunk_rows rows (the last one takes the rest)");
-      geo_v.k = (uint32_t)num_chunks;
-      geo_v.sz = opts.chunk_rows;
-      geo_v.rows_last = n - (num_chunks - 1) * opts.chunk_rows;
+      geo_v.k = (uint32_t)num_chunks; geo_v.sz = opts.chunk_rows; geo_v.rows_last = n - (num_chunks - 1) * opts.chunk_rows;
       geo_v.payload_bytes = data_len;
       geo = &geo_v;
     }
@@ -453,10 +491,13 @@ struct rh_decode_call {
     r.k = k;
     r.sz = geo ? geo->sz : n / k;
     r.rows_last = geo ? geo->rows_last : n - (uint64_t)(k - 1) * r.sz;
+    payload = geo ? geo->payload_bytes : data_len;
     K = cs.K; nnodes = (int)cs.nodes.size(); nbuf = (int)cs.bufs.size();
     dp = &device_program(s, device);
+  }
 
-    // kernel form: schema-specialised (compiled once per schema, cached) or the generic interpreter
+  // 2. kernel form: schema-specialised (compiled once per schema, cached) or the generic interpreter; with it, the tiles
+  void choose_kernels() {
     const int mode = opts.flags & 3;
     // the specialised kernels address every chunk buffer with 32-bit byte offsets
     // (every chunk buffer below 4 GiB: at most max_row_bytes per row -- 16 unless the schema has a wider fixed)
@@ -495,29 +536,30 @@ struct rh_decode_call {
     const uint64_t nblocks64 = n == 0 ? 0 : (uint64_t)(k - 1) * bpc64 + (r.rows_last + tile - 1) / tile;
     if (nblocks64 > 0x7FFFFFFFull / std::max(K, 1)) throw std::invalid_argument("too many records for one call");
     nblocks = (uint32_t)nblocks64;
+  }
 
-    // ---- control block: [first_bad u64 | layout flag, ticket | arena bytes | pad][totals u64 K*k][nullcount u32 nnodes*k*null_slots]
-    //      workspace: errinfo | blocksum | blockbase | tileflag | lanecnt
-    o_tot = 48;      // control words first (program.h): first_bad, layout flag, arena bytes used, pad; words 8..11 = the tile statistics (summed by rh_k_scan_layout / rh_k_tile_stats, kernels.hip)
-    o_tick = o_tot + 8ull * K * k;                    // [k] tile tickets of the single-pass form (zero like the rest of the block)
-    o_null = align_up(o_tick + 4ull * k, 16);
-    null_slots = rh::null_slots_for(k);
-    // (with one null-count slot -- k > 2048 chunks -- the slot area is no larger than the compact host layout, whose publish
-    //  token sits behind the summed counts: room for it, whatever the rounding)
-    ctrl_bytes = align_up(std::max<uint64_t>(o_null + 4ull * nnodes * k * null_slots, align_up(o_null + 4ull * nnodes * k, 8) + 8), kAlign);
-    const uint64_t o_err = 0;       // the rest lives in the workspace (needs no zeroing)
-    const uint64_t o_bsum = align_up(o_err + sizeof(rh::ErrInfo) * (uint64_t)nblocks, kAlign);
+  // 3. the control block (zeroed, CtrlPool; laid out by call_plan.h ctrl_plan), the workspace and the buffer tables; KParams over them
+  void place_blocks() {
+    const bool ranged = size_r && emit_r;
+    cp = ctrl_plan(K, nnodes, k);
+    // workspace (needs no zeroing): errinfo | blocksum | blockbase | tileflag | lanecnt
+    const uint64_t o_bsum = align_up(sizeof(rh::ErrInfo) * (uint64_t)nblocks, kAlign);
     const uint64_t o_bbase = align_up(o_bsum + 4ull * K * nblocks, kAlign);
     const uint64_t o_flag = align_up(o_bbase + 4ull * K * nblocks, kAlign);
     const uint64_t o_lcnt = align_up(o_flag + 4ull * nblocks, kAlign);
     // (per-record counters from the size pass to the emit pass: two per dword for the specialised kernels, one for the generic ones)
     const uint64_t o_lcnt32 = align_up(o_lcnt + 4ull * (sk ? (uint64_t)((cs.KL + 1) / 2) : (uint64_t)cs.KL) * nblocks * tile, kAlign);
-    const uint64_t o_wl = align_up(o_lcnt32 + ((size_r && emit_r) ? 4ull * (uint64_t)cs.KL * nblocks * tile : 0), kAlign);      // (+ the ranged pair's 32-bit counters)
-    const uint64_t ws_bytes = align_up(o_wl + ((size_r && emit_r) ? 8ull + 8ull * nblocks : 0), kAlign);                           // (+ its work list: large tiles first)
+    const uint64_t o_wl = align_up(o_lcnt32 + (ranged ? 4ull * (uint64_t)cs.KL * nblocks * tile : 0), kAlign);      // (+ the ranged pair's 32-bit counters)
+    const uint64_t ws_bytes = align_up(o_wl + (ranged ? 8ull + 8ull * nblocks : 0), kAlign);                           // (+ its work list: large tiles first)
     hp.mark("setup");
     ws = Lease(dev_pool(), ws_bytes, device);
-    hctrl = Lease(pin_pool(), ctrl_bytes, device);
-    ctrl.reset(new CtrlLease(ctrl_bytes, device, stream));        // all zero (CtrlPool)
+    hctrl = Lease(pin_pool(), cp.bytes, device);
+    ctrl.reset(new CtrlLease(cp.bytes, device, stream));        // all zero (CtrlPool)
+    // the buffer tables [chunk][buf]: pointers, then sizes -- written by the layout kernel, or by the host (exact_tail)
+    n_entries = (uint64_t)k * std::max(nbuf, 0);
+    tab_bytes = align_up((uint64_t)std::max(nbuf, 1) * k * 16, kAlign);
+    dtab = Lease(dev_pool(), tab_bytes, device);
+    d_sizes = (uint64_t*)(dtab.ptr() + (uint64_t)std::max(nbuf, 1) * k * 8);
     hp.mark("leases");
 
     std::memset(&P, 0, sizeof P);
@@ -526,105 +568,47 @@ struct rh_decode_call {
     P.prog = dp->prog; P.sym_off = dp->sym_off; P.sym_data = dp->sym_data;
     P.nops = (int)cs.prog.size(); P.K = K; P.KL = cs.KL; P.tile = (uint32_t)tile; P.ndom = cs.ndom; P.nnodes = nnodes; P.list_depth = cs.list_depth;
     P.nbuf = nbuf; P.cnt_databuf = dp->cnt_databuf;
-    P.ranged = (size_r && emit_r) ? 1u : 0u;
+    P.ranged = ranged ? 1u : 0u;
     P.first_bad = (unsigned long long*)ctrl->ptr();
-    P.nullcount = (uint32_t*)(ctrl->ptr() + o_null);
-    P.null_slots = null_slots;
-    P.totals = (uint64_t*)(ctrl->ptr() + o_tot);
-    P.tickets = (uint32_t*)(ctrl->ptr() + o_tick);
-    P.errinfo = (rh::ErrInfo*)(ws.ptr() + o_err);
+    P.nullcount = (uint32_t*)(ctrl->ptr() + cp.o_null);
+    P.null_slots = cp.null_slots;
+    P.totals = (uint64_t*)(ctrl->ptr() + cp.o_tot);
+    P.tickets = (uint32_t*)(ctrl->ptr() + cp.o_tick);
+    P.errinfo = (rh::ErrInfo*)ws.ptr();
     P.blocksum = (uint32_t*)(ws.ptr() + o_bsum);
     P.blockbase = (uint32_t*)(ws.ptr() + o_bbase);
     P.tileflag = (uint32_t*)(ws.ptr() + o_flag);
     P.lanecnt = (uint32_t*)(ws.ptr() + o_lcnt);
     P.lanecnt32 = (uint32_t*)(ws.ptr() + o_lcnt32);
-    // (a projection without variable-length output that dropped variable-length fields keeps its size pass: schema.h size_always)
-    const bool size_pass = K > 0 || cs.size_always;
-    P.worklist = (P.ranged && size_pass && n > 0) ? (uint32_t*)(ws.ptr() + o_wl) : nullptr;      // (filled by the size kernel: only with a size pass)
-    P.bigmark = P.worklist ? P.worklist + 2 + nblocks : nullptr;
-
-    // LDS: fixed part + input window sized from the mean record length (falls back to global reads
-    // for workgroups whose 256 records do not fit)
-    const uint32_t lds_fixed = (sk ? rh::spec_lds_fixed_words_host(K, nnodes, (int)(tile / 64), rh::child_bitmap_count(cs), rh::dense_list_count(cs), rh::dom0_bitmap_count(cs)) * 4 : rh_lds_fixed_bytes(K, cs.KL, (int)tile, cs.list_depth, nnodes, nbuf)) + 16;   // + window slack
-    payload = geo ? geo->payload_bytes : data_len;
-    const uint64_t avg = n ? payload / n + 1 : 16;
-    // (tuning / test knobs, read per call: RUHVRO_HIP_WIN_PCT, RUHVRO_HIP_WIN_PAD)
-    const uint64_t win_pct = (uint64_t)env_long("RUHVRO_HIP_WIN_PCT", 115, 100, 400);
-    const uint64_t win_pad = (uint64_t)env_long("RUHVRO_HIP_WIN_PAD", 2048, 0, 65536);
-    uint64_t win = align_up(avg * tile * win_pct / 100 + win_pad * tile / rh::kBlock, 16);
-    win = std::max<uint64_t>(win, 8192 * tile / rh::kBlock);
-    const uint64_t lds_cap = 160 * 1024 - 512;
-    if (lds_fixed + 4096 > lds_cap) throw rh::SchemaError("schema needs more LDS than a CDNA4 workgroup has");
-    win = std::min<uint64_t>(win, std::min<uint64_t>((lds_cap - lds_fixed) & ~15ull, 96 * 1024));
-    // Occupancy steps: a CU's 160 KB hold N workgroups of at most 160 KB / N each.  A window that puts the workgroup just
-    // above a step costs a whole workgroup per CU (a quarter of the resident waves at N = 4) for a few hundred bytes of
-    // slack, so it gives that slack up as long as a smaller margin (6 % + 1 KB over the mean tile) is left.
-    if (win_pct == 115 && win_pad == 2048) {       // (not when a test / sweep sets the window by hand)
-      const uint64_t min_win = align_up(avg * tile * 106 / 100 + 1024 * tile / rh::kBlock, 16);
-      for (uint64_t nwg = 4; nwg >= 2; nwg--) {        // (4: what the emit kernel's registers allow at most)
-        const uint64_t step = (160 * 1024 / nwg) & ~511ull;
-        if (lds_fixed + win > step && step > lds_fixed && step - lds_fixed >= min_win) { win = (step - lds_fixed) & ~15ull; break; }
-      }
-      // Round 6: never a window that leaves a CU fewer than four workgroups.  Records too large for it (a mean tile of 40 KB and
-      // more: ~150 B per record) are walked in ranges by the ranged kernels, which keeps sixteen wavefronts per CU resident --
-      // measured on the skewed workload (mean record 393 B): 7.1 ms with a 40 KB window, 10.7 ms with the 100 KB one the mean
-      // tile asks for (profiles/r06_c_*).  Only with the specialised kernels: the generic ones have no ranges.
-      if (sk && !cs.wide) {
-        const uint64_t step4 = (160 * 1024 / 4) & ~511ull;
-        if (step4 > lds_fixed + 8192 && lds_fixed + win > step4) win = (step4 - lds_fixed) & ~15ull;
-      }
-    }
-    // A wide schema's tile is one wavefront: the window is kept small enough for 8 of them per CU (records of a hundred and more
-    // columns are large: a window for 64 of them would leave a CU one or two wavefronts) -- tiles past it are walked in ranges.
-    if (cs.wide && win_pct == 115 && win_pad == 2048) {
-      const uint64_t per_wave = (160 * 1024 / 8) & ~511ull;
-      if (per_wave > lds_fixed + 4096) win = std::min<uint64_t>(win, (per_wave - lds_fixed) & ~15ull);
-    }
-    // (RUHVRO_HIP_WIN_BYTES: the window as given -- 0 = none, every tile is walked from global memory; measurement knob)
-    {
-      const long fixed_win = env_long("RUHVRO_HIP_WIN_BYTES", -1, 0, 150 * 1024);
-      if (fixed_win >= 0) win = std::min<uint64_t>((uint64_t)fixed_win & ~15ull, (lds_cap - lds_fixed) & ~15ull);
-    }
-    P.win_bytes = (uint32_t)win;
-    // (the ranged pair takes LARGE tiles first, program.h KParams::worklist: large = well beyond both the window and this call's mean
-    //  tile -- every tile of a wide schema is several windows)
-    P.big_tile_bytes = (uint64_t)rh::kBigTileWindows * std::max<uint64_t>(win, nblocks ? payload / nblocks : 0);
-    lds_bytes = lds_fixed + (uint32_t)win;
-    // optional in-kernel phase timing of the specialised kernels (RUHVRO_HIP_PROFILE=1)
-    static const bool profile_env = [] { const char* e = std::getenv("RUHVRO_HIP_PROFILE"); return e && *e && *e != '0'; }();
-    profile = profile_env;
-    if (profile && sk) {
-      prof_buf = Lease(dev_pool(), 64 * 32 * 8, device);
-      HIPCHK(hipMemsetAsync(prof_buf.ptr(), 0, 64 * 32 * 8, stream));
-      P.prof = (unsigned long long*)prof_buf.ptr();
-    }
-
-    if (want_stats) ev.init();
-    hp.mark("events");
-
-    // ---- the launch sequence.  With a size history for this schema the whole call is ONE stream submission:
-    //   k_size -> k_scan -> k_layout (exact arena layout on the device, program.h LParams) -> k_init -> k_emit -> one D2H
-    // of the control words.  The arena is reserved up front from the history; when it turns out too small (the data
-    // changed character), the layout kernel says so, init/emit return at once, and the host re-runs the tail with an
-    // exactly sized arena -- which is also what the first call of a schema does.
-    totals.assign((size_t)K * k, 0);
-    n_entries = (uint64_t)k * std::max(nbuf, 0);
-    tab_bytes = align_up((uint64_t)std::max(nbuf, 1) * k * 16, kAlign);
-    dtab = Lease(dev_pool(), tab_bytes, device);
-    d_sizes = (uint64_t*)(dtab.ptr() + (uint64_t)std::max(nbuf, 1) * k * 8);
     P.bufptr = (void* const*)dtab.ptr();
+    // (a projection without variable-length output that dropped variable-length fields keeps its size pass: schema.h size_always)
+    size_pass = K > 0 || cs.size_always;
+    P.worklist = (ranged && size_pass && n > 0) ? (uint32_t*)(ws.ptr() + o_wl) : nullptr;      // (filled by the size kernel: only with a size pass)
+    P.bigmark = P.worklist ? P.worklist + 2 + nblocks : nullptr;
     for (const rh::BufDesc& d : cs.bufs) child_bitmaps = child_bitmaps || (d.kind == rh::BK_BITMAP && d.dom != 0);   // built with atomics on zeroed words
+  }
 
-    const bool two_sync = env_long("RUHVRO_HIP_TWO_SYNC", 0, 0, 1) != 0;
-    // (RUHVRO_HIP_ARENA_PERMILLE: test hook, the arena is reserved as if the schema's history said that many output
-    //  bytes per 1000 input bytes -- a small value forces the LF_CAPACITY retry)
-    const long ratio_hook = env_long("RUHVRO_HIP_ARENA_PERMILLE", -1, 0, 1000000);
-    const double ratio = ratio_hook >= 0 ? std::max(1e-9, ratio_hook / 1000.0) : s->arena_ratio.load();
-    fused = n > 0 && ratio > 0 && !two_sync && n_entries <= (1u << 16);
-    // stage timings (rh_stats) come from the kernels' own start / stop timestamps: e0..e1 = k_size, e5..e2 = k_scan,
-    // e3..e4 = k_emit
-    if (start_after) HIPCHK(hipStreamWaitEvent(stream, start_after, 0));
-    if (try_single(two_sync, ratio_hook)) return;
+  // 4. LDS: the kernels' fixed part + the input window (call_plan.h window_plan; its knobs are read per call)
+  void set_window() {
+    const uint32_t lds_fixed = (sk ? rh::spec_lds_fixed_words_host(K, nnodes, (int)(tile / 64), rh::child_bitmap_count(cs), rh::dense_list_count(cs), rh::dom0_bitmap_count(cs)) * 4 : rh_lds_fixed_bytes(K, cs.KL, (int)tile, cs.list_depth, nnodes, nbuf)) + 16;   // + window slack
+    if (lds_fixed + 4096 > kLdsCap) throw rh::SchemaError("schema needs more LDS than a CDNA4 workgroup has");
+    WindowKnobs kn;      // (tuning / test knobs)
+    kn.pct = (uint64_t)env_long("RUHVRO_HIP_WIN_PCT", 115, 100, 400);
+    kn.pad = (uint64_t)env_long("RUHVRO_HIP_WIN_PAD", 2048, 0, 65536);
+    kn.bytes = env_long("RUHVRO_HIP_WIN_BYTES", -1, 0, 150 * 1024);
+    const WindowPlan w = window_plan(n ? payload / n + 1 : 16, tile, lds_fixed, payload, nblocks, sk != nullptr, cs.wide, kn);
+    P.win_bytes = w.win_bytes;
+    P.big_tile_bytes = w.big_tile_bytes;
+    lds_bytes = lds_fixed + w.win_bytes;
+  }
+
+  // 5. the two-pass form.  With a size history for this schema (`ratio`) the whole call is ONE stream submission:
+  //   k_size -> k_scan -> k_layout (exact arena layout on the device, program.h LParams) -> k_init -> k_emit -> k_publish.
+  // The arena is reserved up front from the history; when it turns out too small (the data changed character), the layout
+  // kernel says so, init/emit return at once, and the host re-runs the tail with an exactly sized arena -- which is also what
+  // the first call of a schema does (finish: exact_tail).
+  // stage timings (rh_stats) come from the kernels' own start / stop timestamps: e0..e1 = k_size, e5..e2 = k_scan, e3..e4 = k_emit
+  void submit_two_pass(double ratio) {
     timed_size = n > 0 && size_pass;
     size_f = sk ? sk->size_fn : nullptr;
     emit_f = sk ? sk->emit_fn : nullptr;
@@ -661,40 +645,45 @@ struct rh_decode_call {
       count(RH_CTR_FUSED_CALLS);
       const uint64_t capacity = align_up((uint64_t)(ratio * basis * 1.125) + n_entries * kAlign + (1u << 20), kAlign);
       r.arena = arena_lease(capacity);
-      rh::LParams LP;
-      std::memset(&LP, 0, sizeof LP);
-      LP.totals = P.totals; LP.desc = dp->desc; LP.sz = r.sz; LP.rows_last = r.rows_last; LP.n = n; LP.k = k;
-      LP.nbuf = nbuf; LP.K = K; LP.ndom = cs.ndom; LP.arena = r.arena.ptr(); LP.capacity = r.arena.b.size;
-      LP.bufptr = (void**)dtab.ptr(); LP.bufsize = d_sizes; LP.ctrl = P.first_bad; LP.narrow = sk ? 1u : 0u;
-      LP.narrow_rows = narrow_rows;
+      const rh::LParams LP = layout_params(P.totals, sk != nullptr);
       // (the tile statistics are summed by the scan launch; a size pass with nothing to scan gets a small launch of its own)
       if (timed_size && K == 0 && rh_launch_tile_stats(ctrl->ptr(), P.tileflag, nblocks, stream)) throw HipError("k_tile_stats launch failed");
       if ((timed_size && K > 0) ? rh_launch_scan_layout(&P, &LP, stream, ev.at(5), ev.at(2)) : rh_launch_layout(&LP, stream))
         throw HipError("k_scan / k_layout launch failed");
       launch_tail(true);                           // the layout kernel wrote offsets[0] = 0 itself
       hp.mark("layout+emit_launch");
-      // the control words go to the host from the call's last kernel, which also re-zeroes the block (rh_k_publish) and
-      // writes a per-call token behind them: finish() spins on that word instead of waiting for a stream event
-      void* hdev = nullptr;
       static const bool no_publish = env_long("RUHVRO_HIP_NO_PUBLISH", 0, 0, 1) != 0;
-      if (!no_publish && hipHostGetDevicePointer(&hdev, hctrl.ptr(), 0) == hipSuccess && hdev) {
-        static std::atomic<uint32_t> next_token{1};
-        token = next_token.fetch_add(1);
-        if (token == 0) token = next_token.fetch_add(1);
-        o_flag_h = align_up(o_null + 4ull * nnodes * k, 8);                 // host layout: head | compact null counts | token
-        *(volatile uint32_t*)(hctrl.ptr() + o_flag_h) = 0;
-        if (rh_launch_publish(ctrl->ptr(), hdev, (uint32_t)(o_null / 4), (uint32_t)(nnodes * (int)k), (uint32_t)(o_flag_h / 4), token, null_slots, stream))
-          throw HipError("k_publish launch failed");
-        ctrl->b.clean = true;
-        published = true;
-      } else {
-        (void)hipGetLastError();
-        HIPCHK(hipMemcpyAsync(hctrl.ptr(), ctrl->ptr(), ctrl_bytes, hipMemcpyDeviceToHost, stream));
-        if (async) done.record(device, stream);
-      }
+      publish_head(!no_publish);
       hp.mark("d2h_enqueue");
     }
     launch_probe();
+  }
+
+  void enqueue() {
+    Range rk("ruhvro_hip:decode_device (k_size, k_scan, k_layout, k_init, k_emit)");
+    chunk_geometry();
+    choose_kernels();
+    place_blocks();
+    set_window();
+    // optional in-kernel phase timing of the specialised kernels (RUHVRO_HIP_PROFILE=1)
+    static const bool profile_env = [] { const char* e = std::getenv("RUHVRO_HIP_PROFILE"); return e && *e && *e != '0'; }();
+    if (profile_env && sk) {
+      prof_buf = Lease(dev_pool(), 64 * 32 * 8, device);
+      HIPCHK(hipMemsetAsync(prof_buf.ptr(), 0, 64 * 32 * 8, stream));
+      P.prof = (unsigned long long*)prof_buf.ptr();
+    }
+    if (want_stats) ev.init();
+    hp.mark("events");
+
+    totals.assign((size_t)K * k, 0);
+    const bool two_sync = env_long("RUHVRO_HIP_TWO_SYNC", 0, 0, 1) != 0;
+    // (RUHVRO_HIP_ARENA_PERMILLE: test hook, the arena is reserved as if the schema's history said that many output
+    //  bytes per 1000 input bytes -- a small value forces the LF_CAPACITY retry)
+    const long ratio_hook = env_long("RUHVRO_HIP_ARENA_PERMILLE", -1, 0, 1000000);
+    const double ratio = ratio_hook >= 0 ? std::max(1e-9, ratio_hook / 1000.0) : s->arena_ratio.load();
+    fused = n > 0 && ratio > 0 && !two_sync && n_entries <= (1u << 16);
+    if (start_after) HIPCHK(hipStreamWaitEvent(stream, start_after, 0));
+    if (!try_single(two_sync, ratio_hook)) submit_two_pass(ratio);
   }
 
   void finish() {
@@ -703,22 +692,10 @@ struct rh_decode_call {
     HIPCHK(hipSetDevice(device));
     if (fused) {
       if (published) {
-        // spin on the token rh_k_publish stores last into this call's pinned block: this call only (later calls stay
-        // queued behind it), no event in the stream, and sooner than a stream wait returns
-        volatile uint32_t* flag = (volatile uint32_t*)(hctrl.ptr() + o_flag_h);
-        for (uint32_t spins = 0; __atomic_load_n(flag, __ATOMIC_ACQUIRE) != token;) {
-          if ((++spins & 0xFFFFu) == 0) {              // a failed launch or a fault must not hang the caller
-            const hipError_t q = hipStreamQuery(stream);
-            if (q == hipSuccess) {                     // everything on the stream is done: the token must be there
-              if (__atomic_load_n(flag, __ATOMIC_ACQUIRE) != token) throw HipError("rh_k_publish finished without publishing its token");
-              break;
-            }
-            if (q != hipErrorNotReady) throw HipError(std::string("stream failed while waiting for a decode call: ") + hipGetErrorString(q));
-          }
-#if defined(__x86_64__)
-          __builtin_ia32_pause();
-#endif
-        }
+        hipError_t q = hipSuccess;
+        const Handover::Seen seen = head.wait(stream, &q);
+        if (seen == Handover::DONE_WITHOUT) throw HipError("rh_k_publish finished without publishing its token");
+        if (seen == Handover::FAILED) throw HipError(std::string("stream failed while waiting for a decode call: ") + hipGetErrorString(q));
       } else if (done.e) {
         done.wait();                               // this call only: later calls stay queued behind it
       } else {
@@ -733,24 +710,22 @@ struct rh_decode_call {
       // only -- the repeat walks every tile and reports the lowest of all.
       if (lflag & rh::LF_NEED_RANGED) {
         ctrl->b.clean = published;
-        s->ranged_calls.store(kRangedKeep, std::memory_order_relaxed);
+        ranged_learn(true);
         r.arena.release();
         if (lean) { lean_count(LC_NEED_RANGED); lean_learn(true); }
         throw NeedRanged();
       }
       check_bad(hctrl.ptr());
       // (a lean call reads its statistics whichever way the head came back: the scan launch summed them into the control block)
-      if (lean && !single) { const uint32_t* stw = (const uint32_t*)(hctrl.ptr() + 32); lean_learn(stw[0] != 0 || stw[2] != 0); }
+      const uint32_t* stw = tile_stats();
+      if (lean && !single) lean_learn(stw[0] != 0 || stw[2] != 0);
       if (published && timed_size && !single) {      // the tile statistics the scan launch summed (include/ruhvro_hip.h RH_CTR_*_TILES)
-        const uint32_t* stw = (const uint32_t*)(hctrl.ptr() + 32);
         count(RH_CTR_TILES, nblocks);
         count(RH_CTR_CAREFUL_TILES, stw[0]); count(RH_CTR_OVER_WINDOW_TILES, stw[1]);
         count(RH_CTR_REWALKED_WAVES, stw[2]); count(RH_CTR_SUBTILED_TILES, stw[3]);
-        // tiles past the window: this schema's next calls launch the ranged pair (and compile it if need be)
-        if (stw[1]) s->ranged_calls.store(kRangedKeep, std::memory_order_relaxed);
-        else { uint32_t v = s->ranged_calls.load(std::memory_order_relaxed); if (v) s->ranged_calls.compare_exchange_weak(v, v - 1, std::memory_order_relaxed); }
+        ranged_learn(stw[1] != 0);
       }
-      if (K > 0) std::memcpy(totals.data(), hctrl.ptr() + o_tot, 8ull * K * k);
+      if (K > 0) std::memcpy(totals.data(), hctrl.ptr() + cp.o_tot, 8ull * K * k);
       if (single) {
         ctrl->b.clean = published;
         if (lflag) {            // a column outgrew its capacity (or the capacity layout was refused): the two-pass path decides
@@ -786,16 +761,16 @@ struct rh_decode_call {
     } else {
       count(RH_CTR_TWO_SYNC_CALLS);      // (this path counts no tile statistics: rh_k_scan sums none)
       if (timed_size) {
-        HIPCHK(hipMemcpyAsync(hctrl.ptr(), ctrl->ptr(), ctrl_bytes, hipMemcpyDeviceToHost, stream));
+        HIPCHK(hipMemcpyAsync(hctrl.ptr(), ctrl->ptr(), cp.bytes, hipMemcpyDeviceToHost, stream));
         HIPCHK(hipStreamSynchronize(stream));
         probe_settle();
         if (*(const uint32_t*)(hctrl.ptr() + 8) & rh::LF_NEED_RANGED) {      // (ahead of the error check, as above)
           ctrl->b.clean = false;
-          s->ranged_calls.store(kRangedKeep, std::memory_order_relaxed);
+          ranged_learn(true);
           throw NeedRanged();
         }
         check_bad(hctrl.ptr());
-        std::memcpy(totals.data(), hctrl.ptr() + o_tot, 8ull * K * k);
+        std::memcpy(totals.data(), hctrl.ptr() + cp.o_tot, 8ull * K * k);
       }
       exact_tail();
     }
@@ -816,18 +791,18 @@ struct rh_decode_call {
     }
     r.nullcount.assign((size_t)nnodes * k, 0);
     if (published) {           // rh_k_publish summed the slots: one word per (node, chunk)
-      std::memcpy(r.nullcount.data(), hctrl.ptr() + o_null, 4ull * nnodes * k);
+      std::memcpy(r.nullcount.data(), hctrl.ptr() + cp.o_null, 4ull * nnodes * k);
     } else {
-      const uint32_t* slots = (const uint32_t*)(hctrl.ptr() + o_null);      // [nnodes][k][null_slots] (program.h)
+      const uint32_t* slots = (const uint32_t*)(hctrl.ptr() + cp.o_null);      // [nnodes][k][null_slots] (program.h)
       for (size_t e = 0; e < (size_t)nnodes * k; e++) {
         uint32_t sum = 0;
-        for (uint32_t sl = 0; sl < null_slots; sl++) sum += slots[e * null_slots + sl];
+        for (uint32_t sl = 0; sl < cp.null_slots; sl++) sum += slots[e * cp.null_slots + sl];
         r.nullcount[e] = sum;
       }
     }
     hp.mark("host_layout");
 
-    if (profile && sk) {
+    if (prof_buf.ptr()) {
       unsigned long long hr[64 * 32], h[32] = {0};
       HIPCHK(hipMemcpy(hr, prof_buf.ptr(), sizeof hr, hipMemcpyDeviceToHost));
       for (int r0 = 0; r0 < 64; r0++)
@@ -853,7 +828,7 @@ struct rh_decode_call {
       st.scan_kernel_ms = (timed_size && !single) ? ev.ms(5, 2) : 0.f;
       st.emit_kernel_ms = n > 0 ? ev.ms(3, 4) : 0.f;
       st.specialized = sk ? 1 : 0;
-      st.lds_bytes = emit_lds;
+      st.lds_bytes = n > 0 ? lds_bytes : 0;      // (of the emit launch: a call without records launches none)
     }
     // the call's scratch goes back to the pools now (the control block is zeroed on its stream, CtrlPool)
     ws.release(); dtab.release(); hctrl.release(); prof_buf.release(); lookback.release(); hcaps.release(); ctrl.reset();
@@ -1029,9 +1004,69 @@ rh_device_result* decode_device_split(rh_schema* s, const uint8_t* d_data, const
   return parent.release();
 }
 
+// The in-call split of a large call (decode_device_split), when its conditions hold; nullptr: the call runs unsplit
+static rh_device_result* try_split(rh_schema* s, const uint8_t* d_data, const uint64_t* d_offsets, uint64_t data_len, uint64_t n,
+                                   uint64_t num_chunks, const rh_opts& o, rh_stats* stats, const ChunkGeo* geo) {
+  const long G = env_long("RUHVRO_HIP_INTERNAL_STREAMS", kInternalStreamsDefault, 1, 8);
+  const long groups_env = env_long("RUHVRO_HIP_SPLIT_GROUPS", 0, 0, 64);      // (> 1 with one stream: the groups run back to back)
+  if (!(G > 1 || groups_env > 1) || geo || stats || n < (uint64_t)env_long("RUHVRO_HIP_SPLIT_MIN", kSplitMinDefault, 1, 1l << 40) ||
+      (o.flags & 3) == RH_KERNEL_GENERIC || !(s->arena_ratio.load() > 0) || env_long("RUHVRO_HIP_TWO_SYNC", 0, 0, 1) != 0 ||
+      env_long("RUHVRO_HIP_ARENA_PERMILLE", -1, 0, 1000000) >= 0)
+    return nullptr;
+  uint64_t k64 = rh_clamp_chunks(n, num_chunks), sz = n / std::max<uint64_t>(k64, 1);
+  if (o.chunk_rows) {        // explicit geometry: refused by the unsplit path when it does not hold
+    if (!explicit_geometry_ok(n, num_chunks, o.chunk_rows)) return nullptr;
+    k64 = num_chunks; sz = o.chunk_rows;
+  }
+  const unsigned g = (unsigned)std::min<uint64_t>((uint64_t)G, k64);
+  if (!(g > 1 || (groups_env > 1 && k64 > 1)) || ((uintptr_t)d_data & 15)) return nullptr;
+  return decode_device_split(s, d_data, d_offsets, data_len, n, o, (uint32_t)k64, sz, n - (k64 - 1) * sz, g);
+}
+
+// ---------------------------------------------------------------------------
+// The fall-back ladder.  A call that cannot finish on its form says so with an engine signal, and is repeated, synchronously,
+// one rung down:
+//   FORM_FIRST     as the caller asked: the single pass if it qualifies, a split over internal streams if that applies
+//   FORM_TWO_PASS  NeedTwoPass (a single-pass call outgrew a capacity): the two-pass form, RH_INTERNAL_TWO_PASS
+//   FORM_GENERIC   NeedWideIndex (a child row domain beyond 32-bit indexing; wide_fallbacks) or NeedRanged (a tile past the LDS
+//                  window met specialised kernels without their ranged pair, which compiles in the background meanwhile;
+//                  ranged_retries): the generic kernels.  Terminal: they raise none of the three.
+// A signal that asks for a rung the call is already on (or past) propagates -- to guarded()'s last handler.  Every repeat comes
+// back settled: a rung below the first clears RH_ASYNC.  The generic rung has ONE flag rule, (flags & ~(3 | RH_ASYNC)) |
+// RH_KERNEL_GENERIC: the engine-internal bits stay, so the repeat of a host call keeps RH_INTERNAL_HOST_ARENA (as a host call in
+// GENERIC mode has it from the start).
+// ---------------------------------------------------------------------------
+enum Form { FORM_FIRST, FORM_TWO_PASS, FORM_GENERIC };
+
+// Called inside a catch (...): the rung the signal in flight asks for, counted.  Anything that is no signal, and a signal `now`
+// cannot follow, is thrown on.
+static Form next_rung(Form now) {
+  try { throw; }
+  catch (const NeedTwoPass&) { if (now != FORM_FIRST) throw; return FORM_TWO_PASS; }
+  catch (const NeedWideIndex&) { if (now == FORM_GENERIC) throw; count(RH_CTR_WIDE_FALLBACKS); }
+  catch (const NeedRanged&) { if (now == FORM_GENERIC) throw; count(RH_CTR_RANGED_RETRIES); }
+  return FORM_GENERIC;
+}
+
+// The call on `form`, and on the rungs below it as long as it asks for them: at most three runs
+static rh_device_result* decode_ladder(rh_schema* s, const uint8_t* d_data, const uint64_t* d_offsets, uint64_t data_len, uint64_t n,
+                                       uint64_t num_chunks, rh_opts o, rh_stats* stats, const ChunkGeo* geo, Form form) {
+  for (;;) {
+    if (form == FORM_TWO_PASS) o.flags = (o.flags & ~RH_ASYNC) | RH_INTERNAL_TWO_PASS;
+    if (form == FORM_GENERIC) o.flags = (o.flags & ~(3 | RH_ASYNC)) | RH_KERNEL_GENERIC;
+    try {
+      if (form == FORM_FIRST)
+        if (rh_device_result* r = try_split(s, d_data, d_offsets, data_len, n, num_chunks, o, stats, geo)) return r;
+      return decode_device_impl1(s, d_data, d_offsets, data_len, n, num_chunks, &o, stats, geo);
+    } catch (...) {
+      form = next_rung(form);
+    }
+  }
+}
+
 // The host's half of an asynchronous call (RH_ASYNC): wait for the stream, check for a malformed record, retry with an
-// exact arena if the reserved one was too small, fall back to the generic kernels if a child row domain needs 64-bit
-// indexing.  Throws what the synchronous call would have thrown; a failed result stays failed.
+// exact arena if the reserved one was too small, and take the call down the ladder if it asks for another form.  Throws what
+// the synchronous call would have thrown; a failed result stays failed.
 void settle(rh_device_result* r) {
   if (r->fail) std::rethrow_exception(r->fail);
   if (!r->parts.empty()) {
@@ -1047,32 +1082,22 @@ void settle(rh_device_result* r) {
   }
   if (!r->pending) return;
   std::unique_ptr<DeviceDecode> call = std::move(r->pending);
-  // the call again, synchronously, on another form: the two-pass form (a single-pass call that outgrew a capacity) or the
-  // generic kernels (a child row domain beyond 32-bit indexing -- which the two-pass repeat may itself run into)
-  auto rerun = [&](int add_flags, bool generic) {
+  try {
+    Form next;
+    try {
+      call->finish();
+      if (call->want_stats) { r->st = call->st; r->has_stats = true; }
+      return;
+    } catch (...) {
+      next = next_rung(FORM_FIRST);
+    }
+    // the call again, synchronously, from the rung it asked for
     if (call->lean) lean_count(LC_RERUNS);
     call->drain();
-    rh_opts o = call->opts;
-    o.flags = generic ? ((o.flags & ~(3 | RH_ASYNC)) | RH_KERNEL_GENERIC) : ((o.flags & ~RH_ASYNC) | add_flags);
     rh_stats st2;
     std::memset(&st2, 0, sizeof st2);
-    std::unique_ptr<rh_device_result> r2;
-    try {
-      r2.reset(decode_device_impl1(call->s, call->d_data, call->d_offsets, call->data_len, call->n, call->num_chunks, &o,
-                                   call->want_stats ? &st2 : nullptr, call->geo));
-    } catch (const NeedWideIndex&) {
-      if (generic) throw;
-      count(RH_CTR_WIDE_FALLBACKS);
-      o.flags = (o.flags & ~3) | RH_KERNEL_GENERIC;
-      r2.reset(decode_device_impl1(call->s, call->d_data, call->d_offsets, call->data_len, call->n, call->num_chunks, &o,
-                                   call->want_stats ? &st2 : nullptr, call->geo));
-    } catch (const NeedRanged&) {      // (the two-pass repeat of a single-pass call, launched without the ranged pair, met a tile past the window)
-      if (generic) throw;
-      count(RH_CTR_RANGED_RETRIES);
-      o.flags = (o.flags & ~3) | RH_KERNEL_GENERIC;
-      r2.reset(decode_device_impl1(call->s, call->d_data, call->d_offsets, call->data_len, call->n, call->num_chunks, &o,
-                                   call->want_stats ? &st2 : nullptr, call->geo));
-    }
+    std::unique_ptr<rh_device_result> r2(decode_ladder(call->s, call->d_data, call->d_offsets, call->data_len, call->n, call->num_chunks,
+                                                       call->opts, call->want_stats ? &st2 : nullptr, call->geo, next));
     call.reset();                                  // (its reference to *r ends here)
     r->arena = std::move(r2->arena);
     r->arena_host = r2->arena_host;
@@ -1082,20 +1107,6 @@ void settle(rh_device_result* r) {
     r->output_bytes = r2->output_bytes; r->tables_done = r2->tables_done;
     r->k = r2->k; r->sz = r2->sz; r->rows_last = r2->rows_last;
     if (r2->has_stats || st2.records) { r->st = st2; r->has_stats = true; }
-  };
-  try {
-    try {
-      call->finish();
-      if (call->want_stats) { r->st = call->st; r->has_stats = true; }
-    } catch (const NeedTwoPass&) {
-      rerun(RH_INTERNAL_TWO_PASS, false);
-    } catch (const NeedWideIndex&) {
-      count(RH_CTR_WIDE_FALLBACKS);
-      rerun(0, true);
-    } catch (const NeedRanged&) {
-      count(RH_CTR_RANGED_RETRIES);
-      rerun(0, true);
-    }
   } catch (...) {
     if (call) call->drain();
     r->arena.release();
@@ -1107,57 +1118,7 @@ void settle(rh_device_result* r) {
 rh_device_result* decode_device_impl(rh_schema* s, const uint8_t* d_data, const uint64_t* d_offsets, uint64_t data_len,
                                      uint64_t n, uint64_t num_chunks, const rh_opts* opts, rh_stats* stats,
                                      const ChunkGeo* geo) {
-  try {
-  try {
-    // in-call overlap (decode_device_split): a large call deals its chunk groups to internal streams
-    const long G = env_long("RUHVRO_HIP_INTERNAL_STREAMS", kInternalStreamsDefault, 1, 8);
-    const long groups_env = env_long("RUHVRO_HIP_SPLIT_GROUPS", 0, 0, 64);      // (> 1 with one stream: the groups run back to back)
-    if ((G > 1 || groups_env > 1) && !geo && !stats && n >= (uint64_t)env_long("RUHVRO_HIP_SPLIT_MIN", kSplitMinDefault, 1, 1l << 40) &&
-        (!opts || (opts->flags & 3) != RH_KERNEL_GENERIC) && s->arena_ratio.load() > 0 && env_long("RUHVRO_HIP_TWO_SYNC", 0, 0, 1) == 0 &&
-        env_long("RUHVRO_HIP_ARENA_PERMILLE", -1, 0, 1000000) < 0) {
-      const rh_opts o = opts ? *opts : default_opts();
-      uint64_t k64 = rh_clamp_chunks(n, num_chunks), sz = n / std::max<uint64_t>(k64, 1);
-      bool ok = true;
-      if (o.chunk_rows) {        // explicit geometry: validated by the unsplit path when it does not hold
-        ok = num_chunks >= 1 && num_chunks <= 0xFFFFFFFFull && (num_chunks - 1) <= n / o.chunk_rows &&
-             !(n > 0 && n == (num_chunks - 1) * o.chunk_rows && num_chunks > 1);
-        k64 = num_chunks; sz = o.chunk_rows;
-      }
-      const unsigned g = (unsigned)std::min<uint64_t>((uint64_t)G, k64);
-      if (ok && (g > 1 || (groups_env > 1 && k64 > 1)) && !((uintptr_t)d_data & 15)) {
-        const uint64_t rows_last = n - (k64 - 1) * sz;
-        try {
-          if (rh_device_result* r = decode_device_split(s, d_data, d_offsets, data_len, n, o, (uint32_t)k64, sz, rows_last, g)) return r;
-        } catch (const NeedWideIndex&) {
-          // (a child row domain beyond 32-bit indexing: the whole call goes to the generic kernels below, unsplit)
-          count(RH_CTR_WIDE_FALLBACKS);
-          rh_opts o2 = o;
-          o2.flags = (o.flags & ~3) | RH_KERNEL_GENERIC;
-          return decode_device_impl1(s, d_data, d_offsets, data_len, n, num_chunks, &o2, stats, geo);
-        }
-      }
-    }
-    return decode_device_impl1(s, d_data, d_offsets, data_len, n, num_chunks, opts, stats, geo);
-  } catch (const NeedTwoPass&) {
-    rh_opts o = default_opts();
-    if (opts) o = *opts;
-    o.flags |= RH_INTERNAL_TWO_PASS;
-    return decode_device_impl1(s, d_data, d_offsets, data_len, n, num_chunks, &o, stats, geo);
-  }
-  } catch (const NeedWideIndex&) {
-    count(RH_CTR_WIDE_FALLBACKS);
-    rh_opts o = default_opts();
-    if (opts) o = *opts;
-    o.flags = RH_KERNEL_GENERIC;
-    return decode_device_impl1(s, d_data, d_offsets, data_len, n, num_chunks, &o, stats, geo);
-  } catch (const NeedRanged&) {      // tiles past the LDS window, no ranged pair yet: this call on the generic kernels (the pair compiles in the background)
-    count(RH_CTR_RANGED_RETRIES);
-    rh_opts o = default_opts();
-    if (opts) o = *opts;
-    o.flags = (o.flags & ~(3 | RH_ASYNC)) | RH_KERNEL_GENERIC;
-    return decode_device_impl1(s, d_data, d_offsets, data_len, n, num_chunks, &o, stats, geo);
-  }
+  return decode_ladder(s, d_data, d_offsets, data_len, n, num_chunks, opts ? *opts : default_opts(), stats, geo, FORM_FIRST);
 }
-
 
 }  // namespace rhe

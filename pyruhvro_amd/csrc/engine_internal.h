@@ -2,7 +2,8 @@
 //   engine.cpp              the C ABI (include/ruhvro_hip.h): schema objects, entry points, stats lines
 //   engine_pools.cpp        device / pinned-host / control-block pools
 //   engine_kernels.cpp      per-device schema programs, specialised kernels (code objects from kernel_jobs.h), error texts
-//   engine_device_call.cpp  one device-resident decode call: the launch sequence, settle, the in-call split
+//   engine_device_call.cpp  one device-resident decode call: the launch sequence, settle, the fall-back ladder, the in-call split
+//   call_plan.h             ... and its arithmetic, free of HIP: explicit chunk geometry, control-block offsets, LDS window policy
 //   engine_host.cpp         host in -> host out: gather, the pipelined chunk groups, the multi-GPU deal
 //   engine_export.cpp       Arrow C Data / C Device Data export, host copies of results
 //   engine_encode.cpp       Arrow -> Avro (rh_encode / rh_encode_device)
@@ -36,6 +37,7 @@ extern "C" hipError_t hipExtModuleLaunchKernel(hipFunction_t f, uint32_t globalW
 
 #include "../../include/ruhvro_hip.h"
 #include "program.h"
+#include "call_plan.h"      // kAlign / align_up, and the plan arithmetic of a decode call
 #include "schema.h"
 #include "specialize.h"
 #include "kernel_jobs.h"
@@ -121,9 +123,6 @@ int device_numa_node(int device);                           // NUMA node of a HI
 void bind_thread_to_node(int node);                         // sched_setaffinity to that node's cpus (cached per thread)
 // pinned blocks are pooled per NUMA node of the device they were allocated under (hipHostMalloc places them there)
 inline int pin_key(int device) { const int n = device_numa_node(device); return n < 0 ? 0 : n; }
-
-constexpr uint64_t kAlign = 256;
-inline uint64_t align_up(uint64_t v, uint64_t a) { return (v + a - 1) / a * a; }
 
 // ---------------------------------------------------------------------------
 // caching device / pinned-host pools (one per process; blocks are reused across calls so a

@@ -96,6 +96,8 @@ def single_pass_schemas() -> List[str]:
     out = [SCHEMAS[k] for k in ("full", "cfg3", "flat4", "array_and_map", "nullable_primitives", "t_enum", "t_union")]
     if hasattr(cases, "form_switch_schemas"):      # (tests/test_form_switch.py: single pass -> two pass -> generic)
         out += [cases.form_switch_schema("id_str", "_single"), cases.form_switch_full_skewed_schema()]
+    if hasattr(cases, "form_switch_full_wide_index_schema"):      # (single pass -> two pass -> wide indexing)
+        out += [cases.form_switch_full_wide_index_schema(), cases.form_switch_full_wide_index_schema("_async")]
     return out
 
 

@@ -622,9 +622,16 @@ def form_switch_full_skewed_schema() -> str:
     return json.dumps(dict(json.loads(SCHEMAS["full_skewed"]), name="FormSwitch_full_skewed"))
 
 
+def form_switch_full_wide_index_schema(tag: str = "") -> str:
+    """The full schema under a name of its own, for the single-pass call whose two-pass repeat needs wide indexing (the same
+    reason: no other test's cool-down or history in its way -- nor that of the test's own first fail-over, hence the tag)."""
+    return json.dumps(dict(json.loads(SCHEMAS["full"]), name="FormSwitch_full_wide_index" + tag))
+
+
 def form_switch_schemas() -> List[str]:
     """Every schema tests/test_form_switch.py decodes (scripts/known_schemas.py compiles their kernels ahead of a GPU run)."""
-    return [form_switch_schema(kind, tag) for kind in FORM_SWITCH_KINDS for tag in FORM_SWITCH_TAGS] + [form_switch_full_skewed_schema()]
+    return ([form_switch_schema(kind, tag) for kind in FORM_SWITCH_KINDS for tag in FORM_SWITCH_TAGS] +
+            [form_switch_full_skewed_schema(), form_switch_full_wide_index_schema(), form_switch_full_wide_index_schema("_async")])
 
 
 @functools.lru_cache(maxsize=None)

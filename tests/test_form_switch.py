@@ -21,7 +21,7 @@ import pytest
 
 import cases
 from arrow_compare import assert_batches_identical
-from avrogen import fastgen
+from avrogen import fastgen, synth
 from avrogen.schemas import SCHEMAS
 from oracle import c_walker, py_walker
 from test_tile_stats import T, _geometry, _over_window, _upload
@@ -453,6 +453,43 @@ def test_single_pass_then_two_pass_then_generic(which, monkeypatch):
         print(which, "async" if asynchronous else "sync", {s: d[s] for s in ("single_pass_calls", "single_pass_failovers", "ranged_retries")})
         _same(got, exp)
         assert d["single_pass_calls"] == 1 and d["single_pass_failovers"] == 1 and d["ranged_retries"] == 1, d
+
+
+@pytest.mark.gpu
+def test_single_pass_then_two_pass_then_wide_index(monkeypatch):
+    """A single-pass call whose child row domain outgrows its capacity (the capacities stop below RUHVRO_HIP_NARROW_ROWS) is
+    repeated in the two-pass form; that repeat finds the domain at the bound of 32-bit indexing and is itself repeated on the
+    generic kernels -- in a synchronous call and in the settlement of an asynchronous one.  The full schema under names of its
+    own, 6,000 records in 3 chunks: 2,000 rows per chunk < 2,500 <= ~3,000 child rows per chunk.
+
+    One schema object per call.  With one object for both, the second call never starts on the single pass (measured on the commit
+    before the ladder became one function: single_pass_calls 0, single_pass_failovers 0, wide_fallbacks 1, batches identical): the first call's
+    fail-over is a real LF_CAPACITY one, so the schema sits its next eight calls out (try_single's cool-down)."""
+    recs = synth.records("full", 6000, seed=2)
+    data, offsets = c_walker.pack(recs)
+    exp = c_walker.decode_threaded(recs, cases.form_switch_full_wide_index_schema(), 3)
+    dev = _upload(data, offsets)
+    for asynchronous in (False, True):
+        schema = cases.form_switch_full_wide_index_schema("_async" if asynchronous else "")
+        monkeypatch.delenv("RUHVRO_HIP_NARROW_ROWS", raising=False)
+        # the single-pass kernel loaded, the per-row history of this input recorded
+        r = _device_call(dev, offsets, schema, 3, cabi.KERNEL_SPECIALIZED, single_pass=True)
+        _same(r.to_host(), exp)
+        r.free()
+        monkeypatch.setenv("RUHVRO_HIP_NARROW_ROWS", "2500")
+        c0 = cabi.engine_counters()
+        r = _device_call(dev, offsets, schema, 3, cabi.KERNEL_AUTO, single_pass=True, asynchronous=asynchronous)
+        if asynchronous:
+            r.wait()
+        got = r.to_host()
+        st = r.stats
+        r.free()
+        d = _delta(c0)
+        print("async" if asynchronous else "sync", {s: d[s] for s in ("single_pass_calls", "single_pass_failovers", "wide_fallbacks", "ranged_retries")},
+              "specialized", st["specialized"])
+        _same(got, exp)
+        assert d["single_pass_calls"] == 1 and d["single_pass_failovers"] == 1 and d["wide_fallbacks"] == 1 and d["ranged_retries"] == 0, d
+        assert st["specialized"] == 0, st
 
 
 # ---- 5. split calls ---------------------------------------------------------------------------------------------------------------
