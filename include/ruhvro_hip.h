@@ -488,6 +488,61 @@ int rh_inflate_blocks(const uint8_t* data, uint64_t len, const uint64_t* start, 
 /* The most recent device inflate of this process: GPU time of its two kernels, compressed bytes in, inflated bytes out. */
 void rh_inflate_last(float* size_ms, float* emit_ms, uint64_t* in_bytes, uint64_t* out_bytes);
 
+/* Tolerant container reads.  Added WITHOUT a change of RH_ABI_VERSION (7), discovered by symbol.
+ *
+ * rh_container_salvage is rh_container_scan that goes on past a block it cannot frame: it searches for the next occurrence of
+ * the file's sync marker and frames again behind it.  It fails only where the HEADER does not parse (the messages of
+ * rh_container_scan).  The info object's table (rh_container_info_table) lists the framed blocks; rh_container_info_salvage adds,
+ * per block, the offset of its header and the count its header claims, and `refused` = 1 where that count is one the running
+ * total cannot take ("record count out of range": it counts as 0 in `first`).  A gap is a stretch of bytes in which no block
+ * was framed: [offset, offset + length), `block` = the blocks framed in front of it, `message` = what rh_container_scan says
+ * at `offset`.  Blocks and gaps tile [header_end, len) exactly.  On a file rh_container_scan accepts the table is the same and
+ * there are no gaps.  `steps`: loop turns of the scan (linear in len whatever the bytes are). */
+int rh_container_salvage(const uint8_t* data, uint64_t len, rh_container_info** info, char** err);
+int rh_container_info_salvage(const rh_container_info* i, uint64_t* header_end, const uint64_t** header_offset, const uint64_t** count,
+                              const uint8_t** refused, uint64_t* gaps, uint64_t* steps);
+int rh_container_info_gap(const rh_container_info* i, uint64_t k, uint64_t* offset, uint64_t* length, uint64_t* block, const char** message);
+/* What became of one block of a tolerant blocks call.  code: 0 = sound (kept = its count); an ErrCode (1 .. 0xFF) = record `kept`
+ * is malformed, detail as rh_validate's; RH_BLOCK_END = its records end at byte `detail` of its `aux` bytes (kept = its count);
+ * RH_BLOCK_DROPPED = the caller passed it in as dropped; RH_BLOCK_COUNT / RH_BLOCK_TOO_LARGE = its count / size is refused,
+ * detail = its (inflated) size; RH_BLOCK_INFLATE + an RH_INFLATE_* code = its deflate stream is refused, aux and detail the
+ * rh_inflate_status's reason and detail.  rh_block_status_message: the message the strict call raises for that block (`count` =
+ * what its header claims); release with rh_free_string. */
+#define RH_BLOCK_END 0x100
+#define RH_BLOCK_DROPPED 0x200
+#define RH_BLOCK_COUNT 0x201
+#define RH_BLOCK_TOO_LARGE 0x202
+#define RH_BLOCK_INFLATE 0x300
+typedef struct rh_block_status {
+  uint32_t code;
+  uint32_t aux;
+  int64_t detail;
+  uint64_t kept;
+} rh_block_status;
+int rh_block_status_message(uint64_t block, const rh_block_status* status, uint64_t count, char** message);
+/* rh_decode_cblocks / rh_decode_cblocks_device in the tolerant form: a block that fails costs the call that block's failing
+ * records, not the call.  A block with dropped[b] != 0 (dropped may be NULL), a block whose count or size the strict call
+ * refuses and a block whose deflate stream is refused are not walked and keep nothing; rh_k_split_salvage walks the others,
+ * every lane stopping its own block at its first malformed record; what is kept is gathered into one buffer
+ * (rh_k_salvage_gather) and decoded as rh_decode_device decodes it -- the batches are those of the kept records, in file order,
+ * chunked by num_chunks.  status[nb] says what became of every block.  A call in which nothing is reported launches no gather.
+ * More than max_errors reports -- the blocks with a non-zero code plus extra_errors, the caller's own (gaps) -- set *too_many
+ * = 1 and return RH_OK with no result: the caller runs the strict call for its error.  Failures that belong to no block fail
+ * the call as they fail the strict one, and so do its refusals (devices, RH_ASYNC, chunk_rows).  rh_decode_blocks_tolerant
+ * writes at most out_cap chunks (rh_clamp_chunks(first[nb], num_chunks) always suffices). */
+int rh_decode_blocks_tolerant(const rh_schema* s, const uint8_t* data, uint64_t len, const uint64_t* start, const uint64_t* end,
+                              const uint64_t* first, const uint8_t* dropped, uint64_t nb, int codec, uint64_t max_block_bytes,
+                              uint64_t max_errors, uint64_t extra_errors, uint64_t num_chunks, const rh_opts* opts,
+                              struct ArrowArray* out_chunks, uint32_t out_cap, uint32_t* out_k, rh_block_status* status, int* too_many,
+                              rh_stats* stats, char** err);
+int rh_decode_blocks_tolerant_device(const rh_schema* s, const uint8_t* data, uint64_t len, const uint64_t* start, const uint64_t* end,
+                                     const uint64_t* first, const uint8_t* dropped, uint64_t nb, int codec, uint64_t max_block_bytes,
+                                     uint64_t max_errors, uint64_t extra_errors, uint64_t num_chunks, const rh_opts* opts,
+                                     rh_device_result** out, rh_block_status* status, int* too_many, rh_stats* stats, char** err);
+/* The most recent tolerant blocks call of this process: GPU time of its split and of its gather (0 = none ran), the blocks it
+ * reported (extra_errors not among them), the bytes it gathered (0 = the buffer was decoded where it was). */
+void rh_salvage_last(float* split_ms, float* gather_ms, uint64_t* blocks_reported, uint64_t* bytes_gathered);
+
 /* Measurement hook, not part of the drop-in surface: the host-side gather of a `shards`-GPU rh_decode call (every shard's
  * record slices copied into its staging buffer by its own host thread + `threads_per_shard` helpers, all shards at once)
  * without the GPUs -- pageable destinations (pinned = 0, runs on a box with no device), pinned ones (1), or pageable ones placed

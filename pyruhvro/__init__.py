@@ -4,11 +4,15 @@ Same five functions as the reference's PyO3 module (src/lib.rs:150-158); the thr
 keyword-only extensions ``columns=[...]`` (decode only those top-level fields) and ``reader_schema=`` (decode
 writer-encoded records into an evolved schema).  Beside them the tolerant decode: the
 ``*_tolerant`` functions replace malformed records by ``placeholder_datum(schema)`` and report all of them; and the Avro
-object container files: ``container_info`` / ``read_container`` / ``read_container_to_device`` / ``write_container``."""
+object container files: ``container_info`` / ``read_container`` / ``read_container_to_device`` / ``write_container``, and
+``read_container_tolerant`` / ``read_container_to_device_tolerant``, which salvage what a damaged file still holds."""
 from pyruhvro_amd import (  # noqa: F401
     container_info,
     read_container,
     read_container_to_device,
+    read_container_tolerant,
+    read_container_to_device_tolerant,
+    BlockError,
     write_container,
     deserialize_array_tolerant,
     deserialize_array_threaded_tolerant,

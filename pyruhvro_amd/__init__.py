@@ -406,9 +406,11 @@ __all__ = [
     "placeholder_datum", "validate_records", "RecordError", "deserialize_array_tolerant", "deserialize_array_threaded_tolerant",
     "deserialize_binary_array_tolerant",
     "container_info", "read_container", "read_container_to_device", "write_container", "ContainerInfo",
+    "read_container_tolerant", "read_container_to_device_tolerant", "BlockError",
 ]
 
 from .container import ContainerInfo, container_info, read_container, read_container_to_device, write_container  # noqa: E402
+from .container import BlockError, read_container_tolerant, read_container_to_device_tolerant  # noqa: E402
 
 
 def __getattr__(name):      # (RecordError lives beside the ctypes wrappers that build it; cabi needs numpy, imported on first use)

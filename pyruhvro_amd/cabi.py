@@ -989,3 +989,145 @@ def inflate_last() -> dict:
     a, b, c, d = C.c_float(), C.c_float(), C.c_uint64(), C.c_uint64()
     fn(C.byref(a), C.byref(b), C.byref(c), C.byref(d))
     return {"size_ms": a.value, "emit_ms": b.value, "in_bytes": c.value, "out_bytes": d.value}
+
+
+# Tolerant container reads: added like the entry points above, looked up by symbol.
+BLOCK_END, BLOCK_DROPPED, BLOCK_COUNT, BLOCK_TOO_LARGE, BLOCK_INFLATE = 0x100, 0x200, 0x201, 0x202, 0x300
+BLOCK_STATUS = np.dtype([("code", np.uint32), ("aux", np.uint32), ("detail", np.int64), ("kept", np.uint64)])
+
+
+def container_salvage(buf: np.ndarray) -> dict:
+    """rh_container_salvage over a uint8 array -> container_scan's dict for the blocks that are framed, plus "header_end",
+    "header_offset" / "count" (uint64 arrays, per block), "refused" (uint8, per block: 1 = record count out of range),
+    "gaps" ([(offset, length, block, message)], ascending) and "steps".  Raises ValueError("container: ...") for a header that
+    does not parse -- what container_scan raises.  Needs no device."""
+    scan = _container_sym("rh_container_salvage", C.c_int, [C.c_void_p, C.c_uint64, C.POINTER(C.c_void_p), C.POINTER(C.c_char_p)])
+    n = int(np.asarray(buf).size)
+    a = _u8(buf)
+    info, err = C.c_void_p(), C.c_char_p()
+    rc = scan(a.ctypes.data, n, C.byref(info), C.byref(err))
+    if rc != RH_OK:
+        _raise(rc, err)
+    h = info.value
+    try:
+        slen = C.c_uint64()
+        p = _container_sym("rh_container_info_schema", C.c_void_p, [C.c_void_p, C.POINTER(C.c_uint64)])(h, C.byref(slen))
+        schema = C.string_at(p, slen.value).decode("utf-8")
+        codec = C.string_at(_container_sym("rh_container_info_codec", C.c_void_p, [C.c_void_p])(h)).decode("utf-8", "replace")
+        sync = C.string_at(_container_sym("rh_container_info_sync", C.c_void_p, [C.c_void_p])(h), 16)
+        nb = int(_container_sym("rh_container_info_blocks", C.c_uint64, [C.c_void_p])(h))
+        ps, pe, pf = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        table = _container_sym("rh_container_info_table", C.c_int, [C.c_void_p] + [C.POINTER(C.c_void_p)] * 3)
+        if table(h, C.byref(ps), C.byref(pe), C.byref(pf)) != RH_OK:
+            raise RuntimeError("rh_container_info_table failed")
+        hend, ph, pc, pr, ngaps, steps = C.c_uint64(), C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_uint64(), C.c_uint64()
+        more = _container_sym("rh_container_info_salvage", C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)] + [C.POINTER(C.c_void_p)] * 3 +
+                              [C.POINTER(C.c_uint64)] * 2)
+        if more(h, C.byref(hend), C.byref(ph), C.byref(pc), C.byref(pr), C.byref(ngaps), C.byref(steps)) != RH_OK:
+            raise RuntimeError("rh_container_info_salvage failed")
+
+        def arr(ptr, count, dtype=np.uint64):
+            size = np.dtype(dtype).itemsize * count
+            return np.frombuffer(C.string_at(ptr, size), dtype=dtype).copy() if count else np.zeros(0, dtype=dtype)
+        gap = _container_sym("rh_container_info_gap", C.c_int, [C.c_void_p, C.c_uint64] + [C.POINTER(C.c_uint64)] * 3 + [C.POINTER(C.c_char_p)])
+        gaps = []
+        for k in range(ngaps.value):
+            off, ln, blk, msg = C.c_uint64(), C.c_uint64(), C.c_uint64(), C.c_char_p()
+            if gap(h, k, C.byref(off), C.byref(ln), C.byref(blk), C.byref(msg)) != RH_OK:
+                raise RuntimeError("rh_container_info_gap failed")
+            gaps.append((off.value, ln.value, blk.value, msg.value.decode("utf-8", "replace")))
+        meta = {}
+        get = _container_sym("rh_container_info_metadata_get", C.c_int,
+                             [C.c_void_p, C.c_uint32, C.POINTER(C.c_char_p), C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)])
+        for k in range(_container_sym("rh_container_info_metadata_count", C.c_uint32, [C.c_void_p])(h)):
+            key, val, vlen = C.c_char_p(), C.c_void_p(), C.c_uint64()
+            if get(h, k, C.byref(key), C.byref(val), C.byref(vlen)) != RH_OK:
+                raise RuntimeError("rh_container_info_metadata_get failed")
+            meta[key.value.decode("utf-8", "replace")] = C.string_at(val, vlen.value) if vlen.value else b""
+        return {"schema": schema, "codec": codec, "sync": sync, "metadata": meta, "start": arr(ps, nb), "end": arr(pe, nb),
+                "first": arr(pf, nb + 1), "header_end": hend.value, "header_offset": arr(ph, nb), "count": arr(pc, nb),
+                "refused": arr(pr, nb, np.uint8), "gaps": gaps, "steps": steps.value}
+    finally:
+        _container_sym("rh_container_info_free", None, [C.c_void_p])(h)
+
+
+def block_status_message(block: int, status, count: int) -> str:
+    """rh_block_status_message: the message the strict call raises for block `block` whose status is `status` (one element of a
+    BLOCK_STATUS array) and whose header claims `count` records."""
+    fn = _container_sym("rh_block_status_message", C.c_int, [C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_char_p)])
+    one = np.zeros(1, dtype=BLOCK_STATUS)
+    one[0] = status
+    msg = C.c_char_p()
+    rc = fn(block, one.ctypes.data, count, C.byref(msg))
+    if rc != RH_OK:
+        _raise(rc, msg)
+    try:
+        return msg.value.decode("utf-8", "replace")
+    finally:
+        lib().rh_free_string(C.cast(msg, C.c_void_p))
+
+
+_TBLOCKS_LEAD = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_uint64,
+                 C.c_uint64, C.c_uint64, C.c_uint64, C.POINTER(RhOpts)]
+
+
+def _tolerant_args(data, start, end, first, dropped):
+    keep, nbytes, nb = _blocks_args(data, start, end, first)
+    drop = np.zeros(max(nb, 1), dtype=np.uint8)
+    if dropped is not None:
+        drop[:nb] = np.asarray(dropped, dtype=np.uint8)
+    return keep, nbytes, nb, drop, np.zeros(max(nb, 1), dtype=BLOCK_STATUS)
+
+
+def decode_blocks_tolerant(data, start, end, first, schema_json: str, num_chunks: int, codec: int = CODEC_NULL, max_block_bytes: int = 0,
+                           dropped=None, max_errors: int = 1024, extra_errors: int = 0, device: int = -1, kernel: int = KERNEL_AUTO, *,
+                           columns=None, reader_schema=None):
+    """rh_decode_blocks_tolerant -> (list[RecordBatch], status): the batches of the records the blocks keep, and one
+    BLOCK_STATUS per block.  (None, status) = more than max_errors reports."""
+    s = Schema.get(schema_json, columns, reader_schema)
+    fn = _container_sym("rh_decode_blocks_tolerant", C.c_int, _TBLOCKS_LEAD + [C.POINTER(ArrowArray), C.c_uint32, C.POINTER(C.c_uint32), C.c_void_p,
+                                                                              C.POINTER(C.c_int), C.POINTER(RhStats), C.POINTER(C.c_char_p)])
+    keep, nbytes, nb, drop, status = _tolerant_args(data, start, end, first, dropped)
+    cap = lib().rh_clamp_chunks(int(keep[3][-1]), num_chunks)
+    arr = (ArrowArray * cap)()
+    out_k, many, st, err = C.c_uint32(), C.c_int(), RhStats(), C.c_char_p()
+    opts, _keep = make_opts(device, kernel)
+    rc = fn(s.handle, keep[0].ctypes.data, nbytes, keep[1].ctypes.data, keep[2].ctypes.data, keep[3].ctypes.data, drop.ctypes.data, nb, codec,
+            max_block_bytes, max_errors, extra_errors, num_chunks, C.byref(opts), arr, cap, C.byref(out_k), status.ctypes.data, C.byref(many),
+            C.byref(st), C.byref(err))
+    if rc != RH_OK:
+        _raise(rc, err)
+    if many.value:
+        return None, status[:nb]
+    return _import_chunks(arr, out_k.value, s.arrow_schema), status[:nb]
+
+
+def decode_blocks_tolerant_device(data, start, end, first, schema_json: str, num_chunks: int, codec: int = CODEC_NULL,
+                                  max_block_bytes: int = 0, dropped=None, max_errors: int = 1024, extra_errors: int = 0, device: int = -1,
+                                  stream: int = 0, kernel: int = KERNEL_AUTO, *, columns=None, reader_schema=None):
+    """rh_decode_blocks_tolerant_device -> (DeviceResult, status); (None, status) = more than max_errors reports."""
+    s = Schema.get(schema_json, columns, reader_schema)
+    fn = _container_sym("rh_decode_blocks_tolerant_device", C.c_int, _TBLOCKS_LEAD + [C.POINTER(C.c_void_p), C.c_void_p, C.POINTER(C.c_int),
+                                                                                     C.POINTER(RhStats), C.POINTER(C.c_char_p)])
+    keep, nbytes, nb, drop, status = _tolerant_args(data, start, end, first, dropped)
+    out, many, st, err = C.c_void_p(), C.c_int(), RhStats(), C.c_char_p()
+    opts, _keep = make_opts(device, kernel, stream)
+    rc = fn(s.handle, keep[0].ctypes.data, nbytes, keep[1].ctypes.data, keep[2].ctypes.data, keep[3].ctypes.data, drop.ctypes.data, nb, codec,
+            max_block_bytes, max_errors, extra_errors, num_chunks, C.byref(opts), C.byref(out), status.ctypes.data, C.byref(many), C.byref(st),
+            C.byref(err))
+    if rc != RH_OK:
+        _raise(rc, err)
+    if many.value:
+        return None, status[:nb]
+    r = DeviceResult(out.value, s, st.as_dict())
+    r._want_stats = True
+    return r, status[:nb]
+
+
+def salvage_last() -> dict:
+    """rh_salvage_last: the most recent tolerant container read of this process -- GPU time of its split and of its gather, the
+    blocks it reported, the bytes it gathered (0 = no gather ran: the file's bytes were decoded where they were)."""
+    fn = _container_sym("rh_salvage_last", None, [C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)])
+    a, b, c, d = C.c_float(), C.c_float(), C.c_uint64(), C.c_uint64()
+    fn(C.byref(a), C.byref(b), C.byref(c), C.byref(d))
+    return {"split_ms": a.value, "gather_ms": b.value, "blocks_reported": c.value, "bytes_gathered": d.value}

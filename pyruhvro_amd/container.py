@@ -11,13 +11,21 @@ their offsets; the ordinary decode then runs on them.  ``columns=`` and ``reader
 ``deserialize_array_threaded``.  Codecs: ``null`` and ``deflate``; anything else is refused.  A ``deflate`` file is inflated
 either here with ``zlib``, block by block, into one buffer (``inflate="host"``, the default), or on the device: the
 compressed file is uploaded as it is and two kernels inflate its blocks, one wavefront per block (``inflate="device"``, or
-``RUHVRO_HIP_INFLATE=device`` in the environment).  Both roads accept the same streams and raise the same messages.  The
-tolerant functions do not take containers: a malformed record loses its block's boundaries.
+``RUHVRO_HIP_INFLATE=device`` in the environment).  Both roads accept the same streams and raise the same messages.
+
+    batches, errors = pyruhvro.read_container_tolerant("events.avro", 8)   # what a damaged file still holds, and what it lost
+
+The ``*_tolerant`` functions of the record lists do not take containers -- a malformed record loses its block's boundaries, so
+there is nothing to put a placeholder into.  ``read_container_tolerant`` / ``read_container_to_device_tolerant`` salvage at the
+granularity the format provides instead: every sound block is kept, the records in front of a malformed one
+are kept, the read resynchronises on the file's sync marker where a block cannot be framed, and every loss is reported as a
+``BlockError``.
 """
 from __future__ import annotations
 
 import os
 import zlib
+from collections import namedtuple
 from typing import Dict, Optional
 
 MAGIC = b"Obj\x01"
@@ -72,31 +80,46 @@ def container_info(src) -> ContainerInfo:
     return _scan(src)[1]
 
 
-def _inflate(buf, info: ContainerInfo):
-    """A deflate container -> (one buffer of its inflated blocks back to back, the new starts and ends)."""
+def _inflate_block(mv, b: int, lo: int, hi: int, out: bytearray) -> None:
+    """Block b, the raw deflate stream mv[lo:hi], inflated onto `out` in steps.  A stream that is refused raises the
+    ValueError of the strict read; `out` then holds a part of the block, which the caller cuts off."""
+    d = zlib.decompressobj(-15)
+    at = len(out)
+    data = mv[lo:hi]
+    try:
+        while not d.eof:
+            piece = d.decompress(data, min(_INFLATE_STEP, MAX_BLOCK_BYTES - (len(out) - at)))
+            if not piece and not d.unconsumed_tail and not d.eof:
+                raise ValueError(f"container: block {b}: deflate: the stream ends before its final block")
+            out += piece
+            if len(out) - at >= MAX_BLOCK_BYTES:
+                raise ValueError(f"container: block {b}: deflate: it inflates to {MAX_BLOCK_BYTES} bytes or more "
+                                 "(a block of 4 GiB - 16 bytes or more is not supported)")
+            data = d.unconsumed_tail
+    except zlib.error as e:
+        raise ValueError(f"container: block {b}: deflate: {e}") from None
+    if d.unused_data:
+        raise ValueError(f"container: block {b}: deflate: {len(d.unused_data)} bytes behind the end of the stream")
+
+
+def _inflate(buf, info: ContainerInfo, errors=None):
+    """A deflate container -> (one buffer of its inflated blocks back to back, the new starts and ends).  `errors`: a dict
+    that takes {block: message} for the streams that are refused -- such a block is empty -- instead of the first one raising."""
     import numpy as np
     mv = memoryview(buf)
     out = bytearray()      # every block inflates straight into it, in steps: no second copy, and no block past the limit
     start = np.zeros(info.num_blocks, dtype=np.uint64)
     end = np.zeros(info.num_blocks, dtype=np.uint64)
     for b in range(info.num_blocks):
-        d = zlib.decompressobj(-15)
         at = len(out)
-        data = mv[int(info._start[b]):int(info._end[b])]
-        try:
-            while not d.eof:
-                piece = d.decompress(data, min(_INFLATE_STEP, MAX_BLOCK_BYTES - (len(out) - at)))
-                if not piece and not d.unconsumed_tail and not d.eof:
-                    raise ValueError(f"container: block {b}: deflate: the stream ends before its final block")
-                out += piece
-                if len(out) - at >= MAX_BLOCK_BYTES:
-                    raise ValueError(f"container: block {b}: deflate: it inflates to {MAX_BLOCK_BYTES} bytes or more "
-                                     "(a block of 4 GiB - 16 bytes or more is not supported)")
-                data = d.unconsumed_tail
-        except zlib.error as e:
-            raise ValueError(f"container: block {b}: deflate: {e}") from None
-        if d.unused_data:
-            raise ValueError(f"container: block {b}: deflate: {len(d.unused_data)} bytes behind the end of the stream")
+        if errors is None:
+            _inflate_block(mv, b, int(info._start[b]), int(info._end[b]), out)
+        elif b not in errors:      # (a block that is dropped already is not inflated)
+            try:
+                _inflate_block(mv, b, int(info._start[b]), int(info._end[b]), out)
+            except ValueError as e:
+                errors[b] = str(e)
+                del out[at:]
         start[b], end[b] = at, len(out)
     return np.frombuffer(out, dtype=np.uint8) if out else np.zeros(0, dtype=np.uint8), start, end
 
@@ -157,6 +180,101 @@ def read_container_to_device(src, num_chunks=1, device: int = -1, *, columns=Non
         r = cabi.decode_blocks_device(buf, start, end, info._first, info.schema, num_chunks, device=device, kernel=P._kernel_mode,
                                       columns=columns, reader_schema=reader_schema)
     return DeviceDecode(r, cabi.Schema.get(info.schema, columns, reader_schema).arrow_schema)
+
+
+BlockError = namedtuple("BlockError", ["block", "offset", "length", "kept", "lost", "message"])
+BlockError.__doc__ = """One entry of a tolerant container read's ``errors``.  A damaged block: ``block`` = its index among the blocks that
+were framed, ``offset`` = the first byte of its header, ``length`` = header + payload + marker, ``kept`` / ``lost`` = the records
+of it that are in the batches / that are not, ``message`` = what ``read_container`` raises for a file in which this is the only
+damage.  A gap -- bytes in which no block could be framed: ``block`` and ``lost`` are None, ``kept`` is 0, ``message`` = what
+the framing scan says where the gap begins."""
+
+
+def _salvage(src, num_chunks, columns, reader_schema, inflate, max_errors):
+    """The tolerant read up to the engine call -> (info, engine arguments, entries known here, claimed counts, table)."""
+    import numpy as np
+    import pyruhvro_amd as P
+    from . import cabi
+    from .device import check_max_errors
+    road = _inflate_road(inflate)
+    P._check_chunks(num_chunks)
+    max_errors = check_max_errors(max_errors)
+    buf = _bytes_of(src)
+    scan = cabi.container_salvage(buf)                       # ValueError "container: ..." for a header that does not parse
+    info = ContainerInfo(scan)
+    P._get_schema(info.schema, columns, reader_schema)
+    nb = info.num_blocks
+    count, hoff = scan["count"], scan["header_offset"]
+    entries = [BlockError(None, off, length, 0, None, msg) for off, length, _, msg in scan["gaps"]]
+    messages = {int(b): f"container: block {int(b)}: record count out of range" for b in np.flatnonzero(scan["refused"])}
+    start, end, codec, data = info._start, info._end, cabi.CODEC_NULL, buf
+    if info.codec == "deflate" and road == "device":
+        codec = cabi.CODEC_DEFLATE
+    elif info.codec == "deflate":
+        data, start, end = _inflate(buf, info, messages)
+    dropped = np.zeros(nb, dtype=np.uint8)
+    for b, msg in messages.items():
+        dropped[b] = 1
+        entries.append(BlockError(b, int(hoff[b]), int(info._end[b]) + 16 - int(hoff[b]), 0, int(count[b]), msg))
+    return info, (data, start, end, info._first, dropped, codec, len(scan["gaps"]), max_errors), entries, count, hoff
+
+
+def _block_errors(info, status, entries, count, hoff):
+    """The engine's per-block status -> the entries it adds, merged with those known before the call, ascending by offset."""
+    import numpy as np
+    from . import cabi
+    for b in np.flatnonzero(status["code"]):
+        b = int(b)
+        st = status[b]
+        if int(st["code"]) == cabi.BLOCK_DROPPED:
+            continue                                         # (listed already: its message was made here)
+        kept = int(st["kept"])
+        entries.append(BlockError(b, int(hoff[b]), int(info._end[b]) + 16 - int(hoff[b]), kept, int(count[b]) - kept,
+                                  cabi.block_status_message(b, st, int(count[b]))))
+    return sorted(entries, key=lambda e: e.offset)
+
+
+def _too_many(src, num_chunks, columns, reader_schema, inflate):
+    """More than max_errors entries: the strict call's error, the lowest one -- from the strict call itself."""
+    read_container(src, num_chunks, columns=columns, reader_schema=reader_schema, inflate=inflate)
+    raise RuntimeError("internal error: the strict read accepts a file in which the tolerant read reports damage")
+
+
+def read_container_tolerant(src, num_chunks=1, *, max_errors=1024, columns=None, reader_schema=None, inflate=None):
+    """Extension.  ``read_container`` that damage in the file does not abort: ``(list[pyarrow.RecordBatch], errors)``.  The
+    batches are exactly ``deserialize_array_threaded(kept, info.schema, num_chunks, ...)`` over the records that are kept, in
+    file order: every record of a sound block, and records ``0 .. j - 1`` of a block whose record ``j`` is malformed (nothing
+    behind a malformed record of the same block can be recovered: nothing says where the next one starts).  Rows are dropped,
+    not replaced.  A block whose count or deflate stream is refused keeps nothing.  Where no block can be framed -- a damaged
+    block header or sync marker, a file cut short -- the read goes on behind the next occurrence of the file's sync marker and
+    the bytes skipped are a gap.  ``errors``: one ``BlockError`` per damaged block and per gap, ascending by offset; more than
+    ``max_errors`` of them raise what ``read_container`` raises.  A header that does not parse raises as it does there."""
+    import pyruhvro_amd as P
+    from . import cabi
+    info, (data, start, end, first, dropped, codec, gaps, max_errors), entries, count, hoff = _salvage(src, num_chunks, columns, reader_schema,
+                                                                                                      inflate, max_errors)
+    batches, status = cabi.decode_blocks_tolerant(data, start, end, first, info.schema, num_chunks, codec, MAX_BLOCK_BYTES, dropped, max_errors,
+                                                  gaps, kernel=P._kernel_mode, columns=columns, reader_schema=reader_schema)
+    if batches is None:
+        _too_many(src, num_chunks, columns, reader_schema, inflate)
+    return batches, _block_errors(info, status, entries, count, hoff)
+
+
+def read_container_to_device_tolerant(src, num_chunks=1, device: int = -1, *, max_errors=1024, columns=None, reader_schema=None, inflate=None):
+    """Extension.  ``read_container_tolerant`` with the Arrow buffers left in HBM: a ``DeviceDecode`` as
+    ``read_container_to_device`` returns, its ``.errors`` the list of ``BlockError``."""
+    import pyruhvro_amd as P
+    from . import cabi
+    from .device import DeviceDecode
+    info, (data, start, end, first, dropped, codec, gaps, max_errors), entries, count, hoff = _salvage(src, num_chunks, columns, reader_schema,
+                                                                                                      inflate, max_errors)
+    r, status = cabi.decode_blocks_tolerant_device(data, start, end, first, info.schema, num_chunks, codec, MAX_BLOCK_BYTES, dropped, max_errors,
+                                                   gaps, device=device, kernel=P._kernel_mode, columns=columns, reader_schema=reader_schema)
+    if r is None:
+        _too_many(src, num_chunks, columns, reader_schema, inflate)
+    dec = DeviceDecode(r, cabi.Schema.get(info.schema, columns, reader_schema).arrow_schema)
+    dec.errors = _block_errors(info, status, entries, count, hoff)
+    return dec
 
 
 def _put_long(out: bytearray, v: int) -> None:

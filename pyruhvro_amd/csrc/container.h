@@ -40,4 +40,43 @@ struct SParams {
   unsigned long long* first_bad;   // [0] ~(lowest failure key), 0 if none
 };
 
+// ---- tolerant container reads (rh_decode_blocks_tolerant) ----------------------------------------------------
+// What EVERY lane of rh_k_split_salvage leaves for its block.  A sound block: {0, 0, count, end}.  A malformed record j:
+// {its ErrCode, its detail, j, the byte at which record j begins}.  Records that end before the block does: {E_BLOCK_END, the
+// byte of the payload at which they ended, count, the byte behind the last record}.
+struct SalvageRec {
+  uint32_t code;
+  uint32_t pad;
+  int64_t detail;
+  uint64_t kept;       // records of the block that passed
+  uint64_t kept_end;   // absolute byte at which the first record that is not kept begins (start <= kept_end <= end)
+};
+
+// rh_k_split_salvage: rh_k_split whose failing lane stops its own block only.  S.err is not written; S.first_bad is (any
+// non-zero value = at least one block has a code, the host then reads `rec`).
+struct SalvageParams {
+  SParams S;
+  SalvageRec* rec;     // out [nb]
+};
+
+// One keeping block of rh_k_salvage_gather: bytes [src, src + len) of the split's buffer go to [dst, dst + len) of the gathered
+// one, zeros to [dst + len, dst_next); record j < kept had offset off[off_first + j] and gets new_off[new_first + j].
+struct GatherJob {
+  uint64_t src, len;
+  uint64_t dst, dst_next;      // dst is a multiple of 16; dst_next - (dst + len) <= 15
+  uint64_t off_first, new_first, kept;
+  uint64_t last;               // 1 = the last keeping block: it writes new_off[new_first + kept] = dst + len
+};
+
+// rh_k_salvage_gather: one wavefront per job.
+struct SalvageGatherParams {
+  const uint8_t* data;         // the split's buffer
+  const uint64_t* off;         // the split's offsets
+  const GatherJob* jobs;       // [njobs]
+  uint32_t njobs;
+  uint8_t* out;                // the gathered buffer (16-byte aligned), out_len bytes
+  uint64_t out_len;
+  uint64_t* new_off;           // [n' + 1]
+};
+
 }  // namespace rh

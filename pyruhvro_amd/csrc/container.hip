@@ -60,7 +60,10 @@ __device__ __forceinline__ void split_walk(const Op* program, const SCtx& c, con
   }
 }
 
-extern "C" __global__ void __launch_bounds__(kBlock) rh_k_split(SParams S) {
+// The body of rh_k_split and of rh_k_split_salvage.  SALVAGE: the lane leaves rec[b] for its block whatever became of it, and
+// S.err is not written; everything else -- the walk, the offsets, the order of the stores -- is the same code.
+template <bool SALVAGE>
+__device__ __forceinline__ void split_body(const SParams& S, SalvageRec* rec) {
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
   const uint32_t tid = threadIdx.x, lane = tid & 63;
   const uint32_t depth = (uint32_t)(S.list_depth > 0 ? S.list_depth : 1);
@@ -87,6 +90,7 @@ extern "C" __global__ void __launch_bounds__(kBlock) rh_k_split(SParams S) {
   int64_t detail = 0;
   unsigned long long key = 0;
   uint64_t j = 0;
+  uint32_t bad_at = 0;      // SALVAGE: where the malformed record began
   for (;;) {
     const bool go = mine && code == 0 && j < cnt;
     if (!__any(go)) break;      // (wave-uniform)
@@ -96,17 +100,64 @@ extern "C" __global__ void __launch_bounds__(kBlock) rh_k_split(SParams S) {
     L.live = go; L.pres = go; L.redo = false; L.la = 0;
     L.pstk = 0; L.lstk = 0; L.sstk = 0;
     split_walk(S.prog, c, src, L);
-    if (go && L.err) { code = L.err; detail = L.edetail; key = split_key_record(f0 + j); }
+    if (go && L.err) { code = L.err; detail = L.edetail; key = split_key_record(f0 + j); bad_at = at; }
     if (!go) L.cur = at;        // (a lane that sat the record out stays where it was)
     j += go ? 1u : 0u;
   }
   if (mine && code == 0 && L.cur != end) { code = E_BLOCK_END; detail = (int64_t)(L.cur - cur0); key = split_key_block(f1); }
   if (mine && code != 0) {
-    SplitErr e; e.code = code; e.pad = 0; e.detail = detail;
-    S.err[b] = e;
+    if constexpr (!SALVAGE) {
+      SplitErr e; e.code = code; e.pad = 0; e.detail = detail;
+      S.err[b] = e;
+    }
     atomicMax(S.first_bad, ~key);
   }
+  if constexpr (SALVAGE) {
+    if (mine) {
+      // j counts the records walked, the malformed one among them; L.cur of a lane that failed is not where a record ends
+      const bool rec_bad = code != 0 && code != E_BLOCK_END;
+      SalvageRec r;
+      r.code = code; r.pad = 0; r.detail = detail;
+      r.kept = rec_bad ? j - 1 : j;
+      r.kept_end = st + (uint64_t)((rec_bad ? bad_at : L.cur) - cur0);
+      rec[b] = r;
+    }
+  }
   if (mine && b + 1 == (uint64_t)S.nb) S.offsets[f1] = en;      // offsets[n]: the last record ends with the last block
+}
+
+extern "C" __global__ void __launch_bounds__(kBlock) rh_k_split(SParams S) { split_body<false>(S, nullptr); }
+
+// rh_k_split_salvage: the same walk; a lane that fails stops ITS block and says how far it came.
+extern "C" __global__ void __launch_bounds__(kBlock) rh_k_split_salvage(SalvageParams P) { split_body<true>(P.S, P.rec); }
+
+// rh_k_salvage_gather: what the salvage keeps, made contiguous.  One wavefront per keeping block copies the block's kept run to
+// its 16-byte aligned place (aligned 16-byte stores, loads at whatever alignment the source has, the tail byte by byte), zeroes
+// the pad behind it and rebases the run's record offsets.  Every branch below is wave-uniform but the lane-strided loops and
+// the single-lane stores, and no step is cooperative: a lane that leaves a loop early waits for nobody.
+// Bounds (the host's, engine_container.cpp salvage_and_decode): src + len = kept_end <= the block's end <= the buffer; dst + len <=
+// dst_next <= out_len; new_first + kept <= n'.
+extern "C" __global__ void __launch_bounds__(kBlock) rh_k_salvage_gather(SalvageGatherParams G) {
+  const uint32_t lane = threadIdx.x & 63;
+  const uint64_t w = (uint64_t)blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6);
+  if (w >= (uint64_t)G.njobs) return;
+  const GatherJob J = G.jobs[w];
+  if (J.dst_next > G.out_len || J.len > J.dst_next - J.dst) return;      // (never: the host laid the runs out)
+  const uint8_t* const s = G.data + J.src;
+  uint8_t* const d = G.out + J.dst;
+  const uint64_t nvec = J.len >> 4;
+  for (uint64_t v = lane; v < nvec; v += 64) {
+    const v4w x = *reinterpret_cast<const v4wu*>(s + (v << 4));
+    *reinterpret_cast<v4w*>(d + (v << 4)) = x;
+  }
+  const uint64_t done = nvec << 4;
+  if (done + lane < J.len) d[done + lane] = s[done + lane];          // (fewer than 16 bytes are left)
+  const uint64_t room = J.dst_next - J.dst;
+  if (J.len + lane < room) d[J.len + lane] = 0;                      // (the pad: fewer than 16 bytes)
+  const uint64_t* const off = G.off + J.off_first;
+  uint64_t* const noff = G.new_off + J.new_first;
+  for (uint64_t j = lane; j < J.kept; j += 64) noff[j] = off[j] - J.src + J.dst;
+  if (J.last && lane == 0) noff[J.kept] = J.dst + J.len;
 }
 
 }  // namespace rh
@@ -124,5 +175,24 @@ extern "C" int rh_launch_split(const rh::SParams* S, void* stream) {
   if (e) return e;
   const uint32_t nblocks = (S->nb + rh::kBlock - 1) / rh::kBlock;
   hipLaunchKernelGGL(rh::rh_k_split, dim3(nblocks), dim3(rh::kBlock), lds, (hipStream_t)stream, *S);
+  return (int)hipGetLastError();
+}
+
+extern "C" int rh_launch_split_salvage(const rh::SalvageParams* P, void* stream) {
+  (void)hipGetLastError();
+  if (P->S.nb == 0) return 0;
+  const uint32_t lds = rh_split_lds_bytes(P->S.list_depth);
+  int e = (int)hipFuncSetAttribute(reinterpret_cast<const void*>(rh::rh_k_split_salvage), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+  if (e) return e;
+  const uint32_t nblocks = (P->S.nb + rh::kBlock - 1) / rh::kBlock;
+  hipLaunchKernelGGL(rh::rh_k_split_salvage, dim3(nblocks), dim3(rh::kBlock), lds, (hipStream_t)stream, *P);
+  return (int)hipGetLastError();
+}
+
+extern "C" int rh_launch_salvage_gather(const rh::SalvageGatherParams* G, void* stream) {
+  (void)hipGetLastError();
+  if (G->njobs == 0) return 0;
+  const uint32_t waves_per_group = rh::kBlock / 64;
+  hipLaunchKernelGGL(rh::rh_k_salvage_gather, dim3((G->njobs + waves_per_group - 1) / waves_per_group), dim3(rh::kBlock), 0, (hipStream_t)stream, *G);
   return (int)hipGetLastError();
 }

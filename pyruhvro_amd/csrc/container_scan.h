@@ -26,4 +26,28 @@ struct ContainerInfo {
 // "container: " (and names the block index where there is one); `out` is then unspecified.
 std::string container_scan(const uint8_t* data, uint64_t len, ContainerInfo& out);
 
+// What the salvage scan finds in a damaged file: the blocks that are framed -- count >= 0, size >= 0 that fits
+// in the file, the file's sync marker behind the payload -- and the gaps between them.  Blocks and gaps are ascending, disjoint,
+// and tile [header_end, len) exactly.
+struct SalvageInfo {
+  ContainerInfo info;                    // the header; the table of the framed blocks
+  uint64_t header_end = 0;               // the byte behind the header's sync marker
+  std::vector<uint64_t> header_offset;   // [nb] the first byte of the block's header (its payload ends 16 bytes before the next thing)
+  std::vector<uint64_t> count;           // [nb] the count the block's header claims
+  std::vector<uint8_t> refused;          // [nb] 1 = "record count out of range": the count is not in info.first (it counts as 0 there)
+  struct Gap {
+    uint64_t offset, length;             // the bytes skipped: from the block header that could not be framed to behind the next marker (or to len)
+    uint64_t block;                      // blocks framed in front of it
+    std::string message;                 // what container_scan says at `offset`
+  };
+  std::vector<Gap> gaps;
+  uint64_t steps = 0;                    // loop turns of the scan (outer and search), for the linearity check
+};
+
+// container_scan that goes on past a block it cannot frame: it searches for the next occurrence of the sync marker at or after
+// the failing block header and frames again behind it.  Fails (a message, as container_scan) for a header that does not parse
+// only.  Where container_scan succeeds, out.info is what it fills and there are no gaps.  Every read is checked against `len`;
+// the work is O(len) whatever the bytes are.
+std::string container_salvage(const uint8_t* data, uint64_t len, SalvageInfo& out);
+
 }  // namespace rhc

@@ -9,6 +9,8 @@
 extern "C" {
 uint32_t rh_split_lds_bytes(int list_depth);
 int rh_launch_split(const rh::SParams* S, void* stream);
+int rh_launch_split_salvage(const rh::SalvageParams* P, void* stream);
+int rh_launch_salvage_gather(const rh::SalvageGatherParams* G, void* stream);
 int rh_launch_inflate_size(const rh::InflateParams* P, void* stream);
 int rh_launch_inflate_emit(const rh::InflateParams* P, void* stream);
 }
@@ -17,6 +19,8 @@ using namespace rhe;
 
 struct rh_container_info {
   rhc::ContainerInfo ci;
+  rhc::SalvageInfo sv;      // rh_container_salvage: everything but sv.info, which is moved into ci
+  bool salvaged = false;
 };
 
 namespace rhe {
@@ -49,12 +53,24 @@ static void check_blocks_call(const rh_opts* opts, const uint8_t* data, const ui
 
 static std::string block_where(uint64_t b) { return "container: block " + std::to_string(b) + ": "; }      // (error paths only)
 
+// The messages of a block: built here for the strict calls, which throw them, and for the tolerant ones, which report them.
+static std::string block_large_message(uint64_t b, uint64_t size) {
+  return block_where(b) + "a block of 4 GiB - 16 bytes or more is not supported (" + std::to_string(size) + " bytes)";
+}
+static std::string block_count_message(uint64_t b, uint64_t cnt, uint64_t size) {
+  return block_where(b) + std::to_string(cnt) + " records cannot be in its " + std::to_string(size) + " bytes";
+}
+static std::string block_end_message(uint64_t b, uint64_t cnt, int64_t at, uint64_t size) {
+  return "container: block " + std::to_string(b) + ": its " + std::to_string(cnt) + " records end at byte " + std::to_string(at) + " of " + std::to_string(size);
+}
 // The checks of one block of UNCOMPRESSED bytes: its size, and what bounds a lane's loop, and through it the call's records and
 // its offsets: every record has its minimum wire bytes.
+static bool block_too_large(uint64_t size) { return size >= 0xFFFFFFF0ull; }
+static bool block_count_refused(uint64_t size, uint64_t cnt, uint64_t min_rec) { return min_rec && cnt > size / min_rec; }
+
 static void check_block_size(uint64_t b, uint64_t size, uint64_t cnt, uint64_t min_rec) {
-  if (size >= 0xFFFFFFF0ull) throw DecodeError(block_where(b) + "a block of 4 GiB - 16 bytes or more is not supported (" + std::to_string(size) + " bytes)");
-  if (min_rec && cnt > size / min_rec)
-    throw DecodeError(block_where(b) + std::to_string(cnt) + " records cannot be in its " + std::to_string(size) + " bytes");
+  if (block_too_large(size)) throw DecodeError(block_large_message(b, size));
+  if (block_count_refused(size, cnt, min_rec)) throw DecodeError(block_count_message(b, cnt, size));
 }
 
 // records of no bytes at all (a schema of empty records) are bounded by no byte count: by a count for the whole call, which
@@ -128,8 +144,7 @@ static rh_device_result* split_and_decode(rh_schema* s, rh_schema* plain, Lease&
       const uint64_t fn = key / 2;
       for (uint64_t b = (uint64_t)(std::lower_bound(first + 1, first + nb + 1, fn) - (first + 1)); b < nb && first[b + 1] == fn; b++)
         if (errs[b].code == rh::E_BLOCK_END)
-          throw DecodeError("container: block " + std::to_string(b) + ": its " + std::to_string(first[b + 1] - first[b]) + " records end at byte " +
-                            std::to_string(errs[b].detail) + " of " + std::to_string(end[b] - start[b]));
+          throw DecodeError(block_end_message(b, first[b + 1] - first[b], errs[b].detail, end[b] - start[b]));
       throw std::runtime_error("internal error: the split kernel reported a failure no block owns");
     }
   }
@@ -338,6 +353,227 @@ static rh_device_result* decode_cblocks_impl(rh_schema* s, const uint8_t* data, 
   return split_and_decode(s, plain, I.d_out, I.total, T, istart.data(), iend.data(), first, nb, num_chunks, opts, stats, device, stream, up_ms);
 }
 
+// ---- tolerant reads -------------------------------------------------------------------------------------------
+static_assert(RH_BLOCK_END == rh::E_BLOCK_END, "RH_BLOCK_END is E_BLOCK_END");
+static_assert(sizeof(rh::SalvageRec) == 32 && sizeof(rh::GatherJob) == 64, "device layouts");
+
+static std::mutex g_salvage_last_mu;
+static struct { float split_ms = 0, gather_ms = 0; uint64_t reported = 0, gathered = 0; } g_salvage_last;
+
+static void note_salvage(float split_ms, float gather_ms, uint64_t reported, uint64_t gathered) {
+  std::lock_guard<std::mutex> g(g_salvage_last_mu);
+  g_salvage_last.split_ms = split_ms; g_salvage_last.gather_ms = gather_ms; g_salvage_last.reported = reported; g_salvage_last.gathered = gathered;
+}
+
+static std::string block_status_message(uint64_t b, const rh_block_status& st, uint64_t count) {
+  if (st.code >= 1 && st.code < rh::E_BLOCK_END) {
+    rh::ErrInfo ei; ei.code = st.code; ei.pad = 0; ei.detail = st.detail;
+    return format_error(ei);
+  }
+  if (st.code == RH_BLOCK_END) return block_end_message(b, count, st.detail, st.aux);
+  if (st.code == RH_BLOCK_COUNT) return block_count_message(b, count, (uint64_t)st.detail);
+  if (st.code == RH_BLOCK_TOO_LARGE) return block_large_message(b, (uint64_t)st.detail);
+  if (st.code > RH_BLOCK_INFLATE && st.code <= RH_BLOCK_INFLATE + rhi::ST_TOO_LARGE) {
+    rhi::Status is; is.code = st.code - RH_BLOCK_INFLATE; is.reason = st.aux; is.detail = (uint64_t)st.detail;
+    return inflate_message(b, is);
+  }
+  throw std::invalid_argument("container: a block status without a message");
+}
+
+// The tolerant road from "the bytes are on the device" onward.  start / end / first: the table the lanes walk -- a block that
+// was dropped before the launch has an empty range and no record in it.  status[b].code != 0 marks those; `reported` counts
+// them and the caller's own reports.  nullptr = more than max_errors reports.
+static rh_device_result* salvage_and_decode(rh_schema* s, rh_schema* plain, Lease& d_data, uint64_t len, const std::vector<uint64_t>& start,
+                                            const std::vector<uint64_t>& end, const std::vector<uint64_t>& first, uint64_t nb,
+                                            rh_block_status* status, uint64_t reported, uint64_t extra_errors, uint64_t max_errors,
+                                            uint64_t num_chunks, const rh_opts* opts, rh_stats* stats, int device, hipStream_t stream, float up_ms) {
+  const uint64_t n = first[nb];
+  BlockTable T;
+  T.upload(start.data(), end.data(), first.data(), nb, n, device, stream);
+  Lease d_rec(dev_pool(), sizeof(rh::SalvageRec) * std::max<uint64_t>(nb, 1), device);
+  HIPCHK(hipStreamSynchronize(stream));      // (the table is the caller's frame's)
+  float split_ms = 0;
+  std::vector<rh::SalvageRec> recs;
+  if (nb) {
+    const DeviceProgram& dp = device_program(plain, device);
+    rh::SalvageParams P;
+    std::memset(&P, 0, sizeof P);
+    rh::SParams& S = P.S;
+    S.data = d_data.ptr(); S.data_len = len;
+    S.start = (const uint64_t*)T.d_tab.ptr(); S.end = (const uint64_t*)(T.d_tab.ptr() + T.o_end); S.first = (const uint64_t*)(T.d_tab.ptr() + T.o_first);
+    S.nb = (uint32_t)nb; S.list_depth = plain->cs->list_depth;
+    S.prog = dp.prog; S.sym_off = dp.sym_off; S.sym_data = dp.sym_data;
+    S.offsets = (uint64_t*)T.d_off.ptr();
+    S.err = (rh::SplitErr*)(T.d_tab.ptr() + T.o_err);
+    S.first_bad = (unsigned long long*)(T.d_tab.ptr() + T.o_bad);
+    P.rec = (rh::SalvageRec*)d_rec.ptr();
+    if (rh_split_lds_bytes(S.list_depth) > 160 * 1024 - 512) throw rh::SchemaError("schema needs more LDS than a CDNA4 workgroup has");
+    Events ev;
+    ev.init();
+    ev.rec(0, stream);
+    if (rh_launch_split_salvage(&P, stream)) throw HipError("k_split_salvage launch failed");
+    ev.rec(1, stream);
+    unsigned long long fb = 0;
+    HIPCHK(hipMemcpyAsync(&fb, S.first_bad, 8, hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipStreamSynchronize(stream));
+    split_ms = ev.ms(0, 1);
+    if (fb) {      // at least one lane stopped its block: what every lane left
+      recs.resize(nb);
+      HIPCHK(hipMemcpy(recs.data(), P.rec, sizeof(rh::SalvageRec) * nb, hipMemcpyDeviceToHost));
+    }
+  }
+  g_split_last_ms.store(split_ms);
+  for (uint64_t b = 0; b < nb; b++) {
+    if (status[b].code) continue;      // (dropped before the launch: kept = 0)
+    status[b].kept = first[b + 1] - first[b];
+    if (recs.empty() || !recs[b].code) continue;
+    const rh::SalvageRec& r = recs[b];
+    if (r.kept > first[b + 1] - first[b] || r.kept_end < start[b] || r.kept_end > end[b])
+      throw std::runtime_error("internal error: the salvage split left block " + std::to_string(b) + " a record outside its block");
+    status[b].code = r.code; status[b].aux = r.code == rh::E_BLOCK_END ? (uint32_t)(end[b] - start[b]) : 0u;
+    status[b].detail = r.detail; status[b].kept = r.kept;
+    reported++;
+  }
+  if (reported > max_errors) {
+    note_salvage(split_ms, 0, reported - extra_errors, 0);
+    return nullptr;
+  }
+
+  if (!reported) {      // a clean file: the strict road's buffers as they are
+    note_salvage(split_ms, 0, 0, 0);
+    rh_device_result* r = decode_device_impl(s, d_data.ptr(), (const uint64_t*)T.d_off.ptr(), nb ? end[nb - 1] : 0, n, num_chunks, opts, stats);
+    r->container_data = std::move(d_data);
+    r->container_offsets = std::move(T.d_off);
+    if (stats) stats->h2d_ms += up_ms;
+    return r;
+  }
+
+  // gather_kept: the kept run of every block that keeps a record, each at the next multiple of 16, and the records renumbered
+  std::vector<rh::GatherJob> jobs;
+  uint64_t n2 = 0, at = 0;
+  for (uint64_t b = 0; b < nb; b++) {
+    const uint64_t kept = status[b].kept;
+    if (!kept) continue;
+    const uint64_t kept_end = !recs.empty() && recs[b].code ? recs[b].kept_end : end[b];
+    rh::GatherJob j;
+    j.src = start[b]; j.len = kept_end - start[b];
+    j.dst = at; j.dst_next = align_up(at + j.len, 16);
+    j.off_first = first[b]; j.new_first = n2; j.kept = kept; j.last = 0;
+    jobs.push_back(j);
+    n2 += kept;
+    at = j.dst_next;
+  }
+  if (!jobs.empty()) jobs.back().last = 1;
+  const uint64_t total = at, data_end = jobs.empty() ? 0 : jobs.back().dst + jobs.back().len;
+  Lease d_out(dev_pool(), total + 64, device);
+  Lease d_noff(dev_pool(), 8 * (n2 + 1), device);
+  Lease d_jobs(dev_pool(), sizeof(rh::GatherJob) * std::max<size_t>(jobs.size(), 1), device);
+  HIPCHK(hipMemsetAsync(d_out.ptr() + total, 0, 64, stream));
+  if (jobs.empty()) HIPCHK(hipMemsetAsync(d_noff.ptr(), 0, 8, stream));      // (no wavefront: new_off[0] = 0)
+  else HIPCHK(hipMemcpyAsync(d_jobs.ptr(), jobs.data(), sizeof(rh::GatherJob) * jobs.size(), hipMemcpyHostToDevice, stream));
+  rh::SalvageGatherParams G;
+  std::memset(&G, 0, sizeof G);
+  G.data = d_data.ptr(); G.off = (const uint64_t*)T.d_off.ptr();
+  G.jobs = (const rh::GatherJob*)d_jobs.ptr(); G.njobs = (uint32_t)jobs.size();
+  G.out = d_out.ptr(); G.out_len = total; G.new_off = (uint64_t*)d_noff.ptr();
+  Events ev;
+  ev.init();
+  ev.rec(0, stream);
+  if (rh_launch_salvage_gather(&G, stream)) throw HipError("k_salvage_gather launch failed");
+  ev.rec(1, stream);
+  HIPCHK(hipStreamSynchronize(stream));      // (the jobs are this frame's; the split's buffers go back to the pool)
+  note_salvage(split_ms, ev.ms(0, 1), reported - extra_errors, total);
+  d_data.release();
+  T.d_off.release();
+
+  rh_device_result* r = decode_device_impl(s, d_out.ptr(), (const uint64_t*)d_noff.ptr(), data_end, n2, num_chunks, opts, stats);
+  r->container_data = std::move(d_out);
+  r->container_offsets = std::move(d_noff);
+  if (stats) stats->h2d_ms += up_ms;
+  return r;
+}
+
+static rh_device_result* decode_blocks_tolerant_impl(rh_schema* s, const uint8_t* data, uint64_t len, const uint64_t* start, const uint64_t* end,
+                                                     const uint64_t* first, const uint8_t* dropped, uint64_t nb, int codec, uint64_t max_block_bytes,
+                                                     uint64_t max_errors, uint64_t extra_errors, uint64_t num_chunks, const rh_opts* opts,
+                                                     rh_block_status* status, rh_stats* stats) {
+  if (codec != RH_CODEC_NULL && codec != RH_CODEC_DEFLATE) throw std::invalid_argument("container: codec must be RH_CODEC_NULL or RH_CODEC_DEFLATE");
+  if (nb && !status) throw std::invalid_argument("container: null block status");
+  check_blocks_call(opts, data, start, end, first, nb);
+  rh_schema* const plain = plain_schema(s);
+  const uint64_t min_rec = plain->cs->min_record_bytes;
+  check_compressed_table(start, end, nb, len);
+  for (uint64_t b = 0; b < nb; b++)
+    if (first[b + 1] < first[b]) throw std::invalid_argument(block_where(b) + "negative record count");
+
+  // the table the lanes walk: a block dropped here keeps its place with an empty range and no record
+  std::vector<uint64_t> st(nb), en(nb), fi(nb + 1, 0);
+  uint64_t reported = extra_errors;
+  const auto drop = [&](uint64_t b, uint32_t code, uint32_t aux, int64_t detail) {
+    status[b].code = code; status[b].aux = aux; status[b].detail = detail; status[b].kept = 0;
+    reported++;
+  };
+  for (uint64_t b = 0; b < nb; b++) {
+    status[b] = rh_block_status{0, 0, 0, 0};
+    if (dropped && dropped[b]) drop(b, RH_BLOCK_DROPPED, 0, 0);
+  }
+  // the sizes of uncompressed blocks are known here: a file that cannot pass fails before any device work
+  if (codec == RH_CODEC_NULL) {
+    for (uint64_t b = 0; b < nb; b++) {
+      const uint64_t size = end[b] - start[b], cnt = first[b + 1] - first[b];
+      if (!status[b].code && block_too_large(size)) drop(b, RH_BLOCK_TOO_LARGE, 0, (int64_t)size);
+      if (!status[b].code && block_count_refused(size, cnt, min_rec)) drop(b, RH_BLOCK_COUNT, 0, (int64_t)size);
+      st[b] = start[b];
+      en[b] = status[b].code ? start[b] : end[b];
+      fi[b + 1] = fi[b] + (status[b].code ? 0 : cnt);
+    }
+    check_empty_records(min_rec, fi[nb]);
+    if (reported > max_errors) return nullptr;
+  }
+
+  require_device();
+  int device = 0;
+  if (opts && opts->device >= 0) { HIPCHK(hipSetDevice(opts->device)); device = opts->device; }
+  else HIPCHK(hipGetDevice(&device));
+  hipStream_t stream = opts ? (hipStream_t)opts->stream : nullptr;
+
+  Timer t_up;
+  if (codec == RH_CODEC_NULL) {
+    Lease d_data(dev_pool(), len + 64, device);
+    if (len) HIPCHK(hipMemcpyAsync(d_data.ptr(), data, len, hipMemcpyHostToDevice, stream));
+    HIPCHK(hipMemsetAsync(d_data.ptr() + len, 0, 64, stream));
+    HIPCHK(hipStreamSynchronize(stream));      // (the source is the caller's pageable memory)
+    const float up_ms = t_up.ms();
+    return salvage_and_decode(s, plain, d_data, len, st, en, fi, nb, status, reported, extra_errors, max_errors, num_chunks, opts, stats, device, stream, up_ms);
+  }
+
+  // deflate: the size kernel's verdicts mark the refused streams; they inflate to nothing and hold no record
+  std::vector<uint64_t> cend(end, end + nb);
+  for (uint64_t b = 0; b < nb; b++)
+    if (status[b].code) cend[b] = start[b];      // (a block the caller dropped: no stream to walk)
+  DeviceInflate I;
+  I.size_pass(data, len, start, cend.data(), nb, block_limit_of(max_block_bytes), device, stream);
+  for (uint64_t b = 0; b < nb; b++) {
+    if (status[b].code) { I.status[b].code = rhi::ST_TRUNCATED; continue; }      // (emit_pass gives it no byte)
+    if (I.status[b].code != rhi::ST_OK) drop(b, RH_BLOCK_INFLATE + I.status[b].code, I.status[b].reason, (int64_t)I.status[b].detail);
+  }
+  uint64_t at = 0;
+  for (uint64_t b = 0; b < nb; b++) {
+    const uint64_t size = status[b].code ? 0 : I.size[b], cnt = first[b + 1] - first[b];
+    if (!status[b].code && block_too_large(size)) drop(b, RH_BLOCK_TOO_LARGE, 0, (int64_t)size);
+    if (!status[b].code && block_count_refused(size, cnt, min_rec)) drop(b, RH_BLOCK_COUNT, 0, (int64_t)size);
+    st[b] = at;
+    en[b] = status[b].code ? at : at + size;      // (a block refused for its count is inflated and then not walked)
+    fi[b + 1] = fi[b] + (status[b].code ? 0 : cnt);
+    at += size;
+  }
+  check_empty_records(min_rec, fi[nb]);
+  if (reported > max_errors) return nullptr;
+  I.emit_pass(device, stream);
+  const float up_ms = t_up.ms() - I.size_ms - I.emit_ms;
+  return salvage_and_decode(s, plain, I.d_out, I.total, st, en, fi, nb, status, reported, extra_errors, max_errors, num_chunks, opts, stats, device, stream, up_ms);
+}
+
 }  // namespace rhe
 
 // ===========================================================================
@@ -382,6 +618,104 @@ int rh_container_info_metadata_get(const rh_container_info* i, uint32_t k, const
   return RH_OK;
 }
 void rh_container_info_free(rh_container_info* i) { delete i; }
+
+int rh_container_salvage(const uint8_t* data, uint64_t len, rh_container_info** info, char** err) {
+  if (!info) return RH_ERR_ARGUMENT;
+  *info = nullptr;
+  return guarded(err, [&] {
+    std::unique_ptr<rh_container_info> ci(new rh_container_info);
+    const std::string msg = rhc::container_salvage(data, len, ci->sv);
+    if (!msg.empty()) throw DecodeError(msg);
+    ci->ci = std::move(ci->sv.info);
+    ci->salvaged = true;
+    *info = ci.release();
+    return RH_OK;
+  });
+}
+
+int rh_container_info_salvage(const rh_container_info* i, uint64_t* header_end, const uint64_t** header_offset, const uint64_t** count,
+                              const uint8_t** refused, uint64_t* gaps, uint64_t* steps) {
+  if (!i || !i->salvaged) return RH_ERR_ARGUMENT;
+  if (header_end) *header_end = i->sv.header_end;
+  if (header_offset) *header_offset = i->sv.header_offset.data();
+  if (count) *count = i->sv.count.data();
+  if (refused) *refused = i->sv.refused.data();
+  if (gaps) *gaps = i->sv.gaps.size();
+  if (steps) *steps = i->sv.steps;
+  return RH_OK;
+}
+
+int rh_container_info_gap(const rh_container_info* i, uint64_t k, uint64_t* offset, uint64_t* length, uint64_t* block, const char** message) {
+  if (!i || !i->salvaged || k >= i->sv.gaps.size()) return RH_ERR_ARGUMENT;
+  const rhc::SalvageInfo::Gap& g = i->sv.gaps[k];
+  if (offset) *offset = g.offset;
+  if (length) *length = g.length;
+  if (block) *block = g.block;
+  if (message) *message = g.message.c_str();
+  return RH_OK;
+}
+
+int rh_block_status_message(uint64_t block, const rh_block_status* status, uint64_t count, char** message) {
+  if (!status || !message) return RH_ERR_ARGUMENT;
+  *message = nullptr;
+  return guarded(message, [&] {
+    *message = dup_msg(block_status_message(block, *status, count));
+    return RH_OK;
+  });
+}
+
+int rh_decode_blocks_tolerant_device(const rh_schema* s, const uint8_t* data, uint64_t len, const uint64_t* start, const uint64_t* end,
+                                     const uint64_t* first, const uint8_t* dropped, uint64_t nb, int codec, uint64_t max_block_bytes,
+                                     uint64_t max_errors, uint64_t extra_errors, uint64_t num_chunks, const rh_opts* opts,
+                                     rh_device_result** out, rh_block_status* status, int* too_many, rh_stats* stats, char** err) {
+  if (!s || !out || !too_many) return RH_ERR_ARGUMENT;
+  *out = nullptr;
+  *too_many = 0;
+  return guarded(err, [&] {
+    Timer t;
+    rh_opts pub;
+    if (opts) { pub = *opts; pub.flags &= kPublicFlags; }
+    *out = decode_blocks_tolerant_impl(const_cast<rh_schema*>(s), data, len, start, end, first, dropped, nb, codec, max_block_bytes, max_errors,
+                                       extra_errors, num_chunks, opts ? &pub : nullptr, status, stats);
+    if (!*out) *too_many = 1;
+    if (stats) stats->total_ms = t.ms();
+    return RH_OK;
+  });
+}
+
+int rh_decode_blocks_tolerant(const rh_schema* s, const uint8_t* data, uint64_t len, const uint64_t* start, const uint64_t* end,
+                              const uint64_t* first, const uint8_t* dropped, uint64_t nb, int codec, uint64_t max_block_bytes,
+                              uint64_t max_errors, uint64_t extra_errors, uint64_t num_chunks, const rh_opts* opts,
+                              struct ArrowArray* out_chunks, uint32_t out_cap, uint32_t* out_k, rh_block_status* status, int* too_many,
+                              rh_stats* stats, char** err) {
+  if (!s || !out_chunks || !too_many) return RH_ERR_ARGUMENT;
+  *too_many = 0;
+  if (out_k) *out_k = 0;
+  return guarded(err, [&] {
+    Timer t;
+    rh_opts pub;
+    if (opts) { pub = *opts; pub.flags &= kPublicFlags; }
+    std::unique_ptr<rh_device_result> r(decode_blocks_tolerant_impl(const_cast<rh_schema*>(s), data, len, start, end, first, dropped, nb, codec,
+                                                                    max_block_bytes, max_errors, extra_errors, num_chunks, opts ? &pub : nullptr,
+                                                                    status, stats));
+    if (!r) { *too_many = 1; return (int)RH_OK; }
+    if (r->k > out_cap) throw std::invalid_argument("container: out_chunks has room for " + std::to_string(out_cap) + " chunks, the call made " + std::to_string(r->k));
+    Timer td;
+    const int rc = to_host_impl(r.get(), out_chunks, opts ? (hipStream_t)opts->stream : nullptr);
+    if (stats) stats->d2h_ms = td.ms();
+    if (out_k) *out_k = r->k;
+    if (stats) stats->total_ms = t.ms();
+    return rc;
+  });
+}
+
+void rh_salvage_last(float* split_ms, float* gather_ms, uint64_t* blocks_reported, uint64_t* bytes_gathered) {
+  std::lock_guard<std::mutex> g(g_salvage_last_mu);
+  if (split_ms) *split_ms = g_salvage_last.split_ms;
+  if (gather_ms) *gather_ms = g_salvage_last.gather_ms;
+  if (blocks_reported) *blocks_reported = g_salvage_last.reported;
+  if (bytes_gathered) *bytes_gathered = g_salvage_last.gathered;
+}
 
 float rh_split_last_ms(void) { return g_split_last_ms.load(); }
 

@@ -14,6 +14,10 @@ the upload of the file (rh_stats.h2d_ms) and the export of the results to host m
 `--inflate` measures instead the two roads of a `deflate` file ("Deflate blocks on the device"): the same records at
 ~64 KB and ~1 MB blocks, read_container(inflate="host") and (inflate="device") alternated in one job, medians of 3, with the two
 inflate kernels' GPU times (rh_inflate_last) and the split's beside them -> profiles/container_inflate_10m.json.
+`--tolerant` measures instead the tolerant read against the strict one IN ONE JOB, alternated: the `null` file of
+~64 KB blocks read by read_container, the same clean file by read_container_tolerant, and the same file with 1 % of its blocks
+damaged (12 bytes of 0xFF in the middle of the payload) by read_container_tolerant; medians of `--reps` (default 5) with min and
+max, the salvage's own kernel times (rh_salvage_last) beside them -> profiles/container_salvage_10m.json.  No threshold.
 One JSON object on stdout, also written to --out; the Markdown table on stderr and into DESIGN.md 14, between its two marker
 lines (--design '' leaves the document alone; --from-json FILE rewrites the table from an earlier run's JSON without measuring).
 """
@@ -161,8 +165,82 @@ def inflate_rows(a) -> int:
     return 0
 
 
+def tolerant_rows(a) -> int:
+    """Strict, tolerant on the clean file, tolerant on the damaged file: alternated, the yardstick is the strict row of the same job."""
+    import numpy as np
+    import torch  # noqa: F401  first: the engine shares torch's HIP runtime
+    from avrogen import fastgen
+    from avrogen.schemas import SCHEMAS
+    import pyruhvro_amd as P
+    from pyruhvro_amd import cabi
+
+    t_start = time.perf_counter()
+
+    def note(what):
+        print(f"[{time.perf_counter() - t_start:6.1f} s] {what}", file=sys.stderr, flush=True)
+
+    schema = SCHEMAS["full"]
+    note(f"generating {a.records} records")
+    data, offsets = fastgen.generate("full", a.records)
+    blob, nb = container_of(schema, data, offsets, 64 << 10, "null")
+    del data
+    info = P.container_info(blob)
+    dirty = bytearray(blob)
+    hit = list(range(50, nb, 100))                       # 1 % of the blocks
+    for b in hit:
+        mid = (int(info._start[b]) + int(info._end[b])) // 2
+        dirty[mid:mid + 12] = b"\xff" * 12
+    dirty = bytes(dirty)
+    note(f"{nb} blocks, {len(blob)} bytes, {len(hit)} blocks damaged")
+    reps = a.reps
+    out = {"workload": "full", "records": a.records, "chunks": 8, "reps": reps, "codec": "null", "blocks": nb, "file_bytes": len(blob),
+           "damaged_blocks": len(hit), "rows": {}}
+    old = P.set_kernel_mode("specialized")
+    calls = {"strict": lambda: (P.read_container(blob, 8), []),
+             "tolerant_clean": lambda: P.read_container_tolerant(blob, 8),
+             "tolerant_dirty": lambda: P.read_container_tolerant(dirty, 8, max_errors=nb)}
+    walls = {k: [] for k in calls}
+    last = {k: [] for k in calls}
+    facts = {}
+    for rep in range(-1, reps):                          # (rep -1: every read once, warm)
+        for name, fn in calls.items():
+            t0 = time.perf_counter()
+            batches, errors = fn()
+            ms = (time.perf_counter() - t0) * 1e3
+            note(f"{name}: {ms:.0f} ms")
+            if rep < 0:
+                facts[name] = {"rows": sum(b.num_rows for b in batches), "errors": len(errors), "records_lost": sum(e.lost or 0 for e in errors)}
+            else:
+                walls[name].append(ms)
+                last[name].append(dict(cabi.salvage_last(), split_last_ms=cabi.split_last_ms()))
+            del batches, errors
+    assert facts["tolerant_clean"] == {"rows": a.records, "errors": 0, "records_lost": 0}
+    assert facts["tolerant_dirty"]["rows"] + facts["tolerant_dirty"]["records_lost"] == a.records
+    for name in calls:
+        w = walls[name]
+        row = dict(facts[name], wall_ms=statistics.median(w), wall_ms_min=min(w), wall_ms_max=max(w))
+        row["spread"] = (row["wall_ms_max"] - row["wall_ms_min"]) / row["wall_ms"]
+        row["split_ms"] = statistics.median(k["split_last_ms"] for k in last[name])
+        if name != "strict":
+            row["gather_ms"] = statistics.median(k["gather_ms"] for k in last[name])
+            row["bytes_gathered"] = last[name][0]["bytes_gathered"]
+            row["blocks_reported"] = last[name][0]["blocks_reported"]
+        out["rows"][name] = row
+    for name in ("tolerant_clean", "tolerant_dirty"):
+        out["rows"][name]["over_strict"] = out["rows"][name]["wall_ms"] / out["rows"]["strict"]["wall_ms"]
+    P.set_kernel_mode(old)
+    note("done")
+    text = json.dumps(out, indent=1)
+    print(text)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        open(a.out, "w").write(text + "\n")
+    return 0
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--tolerant", action="store_true", help="the strict and the tolerant read of a clean and of a damaged file (see above); --out defaults to profiles/container_salvage_10m.json")
     ap.add_argument("--inflate", action="store_true", help="the host and the device road of a deflate file (see above); --out defaults to profiles/container_inflate_10m.json")
     ap.add_argument("--design", default=os.path.join(ROOT, "DESIGN.md"), help="the document whose table is rewritten ('' = none)")
     ap.add_argument("--from-json", default=None, help="no measurement: the table of an earlier run's JSON")
@@ -170,6 +248,12 @@ def main():
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "container_full10m.json"))
     a = ap.parse_args()
+    if a.tolerant:
+        if a.out == ap.get_default("out"):
+            a.out = os.path.join(ROOT, "profiles", "container_salvage_10m.json")
+        if a.reps == ap.get_default("reps"):
+            a.reps = 5
+        return tolerant_rows(a)
     if a.inflate:
         if a.out == ap.get_default("out"):
             a.out = os.path.join(ROOT, "profiles", "container_inflate_10m.json")
