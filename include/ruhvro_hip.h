@@ -488,6 +488,30 @@ int rh_inflate_blocks(const uint8_t* data, uint64_t len, const uint64_t* start, 
 /* The most recent device inflate of this process: GPU time of its two kernels, compressed bytes in, inflated bytes out. */
 void rh_inflate_last(float* size_ms, float* emit_ms, uint64_t* in_bytes, uint64_t* out_bytes);
 
+/* Deflate blocks written on the device.  Added WITHOUT a change of RH_ABI_VERSION (7), discovered by symbol.
+ *
+ * rh_deflate_blocks is the twin of rh_inflate_blocks, host in and host out: the nb payloads at data[start[b] .. end[b]) each
+ * become one raw RFC 1951 stream, compressed by rh_k_deflate in segments of 32 KiB (one wavefront each) and gathered back to
+ * back by rh_k_deflate_gather.  *out (malloc'd, release with rh_free_string) holds the streams, stream b at
+ * [out_start[b], out_end[b]); every stream is at most rh_deflate_bound(end[b] - start[b]) bytes.  strategy: which block forms
+ * the writer may choose from -- a segment that would not fit its slot in the form asked for is written stored all the same.
+ * The table is checked as rh_inflate_blocks checks it, before any device work; a payload of 4 GiB - 16 bytes or more is refused
+ * ("container: block b: a block of 4 GiB - 16 bytes or more is not supported (N bytes)"); rh_opts.devices and RH_ASYNC are
+ * refused.  rh_deflate_blocks_host runs the same stream logic (pyruhvro_amd/csrc/deflate_core.h) on the calling thread, with no
+ * device: its bytes are the device's bytes. */
+#define RH_DEFLATE_AUTO 0
+#define RH_DEFLATE_STORED 1
+#define RH_DEFLATE_FIXED 2
+#define RH_DEFLATE_DYNAMIC 3
+int rh_deflate_blocks(const uint8_t* data, uint64_t len, const uint64_t* start, const uint64_t* end, uint64_t nb, uint32_t strategy,
+                      const rh_opts* opts, uint8_t** out, uint64_t* out_len, uint64_t* out_start, uint64_t* out_end, char** err);
+int rh_deflate_blocks_host(const uint8_t* data, uint64_t len, const uint64_t* start, const uint64_t* end, uint64_t nb, uint32_t strategy,
+                           uint8_t** out, uint64_t* out_len, uint64_t* out_start, uint64_t* out_end, char** err);
+/* The largest size a stream for len bytes can take: len + 10 * max(1, ceil(len / 32768)) - 5. */
+uint64_t rh_deflate_bound(uint64_t len);
+/* The most recent device deflate of this process: GPU time of its two kernels, payload bytes in, stream bytes out. */
+void rh_deflate_last(float* deflate_ms, float* gather_ms, uint64_t* in_bytes, uint64_t* out_bytes);
+
 /* Tolerant container reads.  Added WITHOUT a change of RH_ABI_VERSION (7), discovered by symbol.
  *
  * rh_container_salvage is rh_container_scan that goes on past a block it cannot frame: it searches for the next occurrence of

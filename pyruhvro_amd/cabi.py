@@ -991,6 +991,65 @@ def inflate_last() -> dict:
     return {"size_ms": a.value, "emit_ms": b.value, "in_bytes": c.value, "out_bytes": d.value}
 
 
+# Deflate blocks written on the device: added like the entry points above, looked up by symbol.
+DEFLATE_AUTO, DEFLATE_STORED, DEFLATE_FIXED, DEFLATE_DYNAMIC = 0, 1, 2, 3
+DEFLATE_SEGMENT = 32768      # deflate_core.h kSegment: a payload is compressed in independent pieces of this many bytes
+_DEFLATE_LEAD = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32]
+_DEFLATE_TAIL = [C.POINTER(C.c_void_p), C.POINTER(C.c_uint64), C.c_void_p, C.c_void_p, C.POINTER(C.c_char_p)]
+
+
+def _deflate_call(fn, data, start, end, strategy, opts):
+    if isinstance(data, (bytes, bytearray, memoryview)):
+        data = np.frombuffer(data, dtype=np.uint8)
+    n = int(np.asarray(data).size)
+    data = _u8(data)
+    start = np.ascontiguousarray(start, dtype=np.uint64)
+    end = np.ascontiguousarray(end, dtype=np.uint64)
+    if len(start) != len(end):
+        raise ValueError("container: the block table needs as many starts as ends")
+    nb = len(start)
+    out_start, out_end = np.zeros(max(nb, 1), dtype=np.uint64), np.zeros(max(nb, 1), dtype=np.uint64)
+    one = np.zeros(1, dtype=np.uint64)
+    out, out_len, err = C.c_void_p(), C.c_uint64(), C.c_char_p()
+    lead = (data.ctypes.data, n, (start if nb else one).ctypes.data, (end if nb else one).ctypes.data, nb, strategy)
+    tail = (C.byref(out), C.byref(out_len), out_start.ctypes.data, out_end.ctypes.data, C.byref(err))
+    rc = fn(*lead, *opts, *tail)
+    if rc != RH_OK:
+        _raise(rc, err)
+    try:
+        blob = C.string_at(out.value, out_len.value) if out_len.value else b""
+    finally:
+        lib().rh_free_string(C.cast(out, C.c_void_p))
+    return blob, out_start[:nb], out_end[:nb]
+
+
+def deflate_blocks(data, start, end, strategy: int = DEFLATE_AUTO, device: int = -1):
+    """rh_deflate_blocks: the payloads at data[start[b] .. end[b]) each compressed on the device into one raw RFC 1951 stream ->
+    (blob, out_start, out_end): the streams back to back (bytes) and where each lies (uint64 arrays).  strategy: DEFLATE_*."""
+    fn = _container_sym("rh_deflate_blocks", C.c_int, _DEFLATE_LEAD + [C.POINTER(RhOpts)] + _DEFLATE_TAIL)
+    opts, _keep = make_opts(device, KERNEL_AUTO)
+    return _deflate_call(fn, data, start, end, strategy, (C.byref(opts),))
+
+
+def deflate_blocks_host(data, start, end, strategy: int = DEFLATE_AUTO):
+    """rh_deflate_blocks_host: deflate_blocks by the same stream logic on the calling thread -- the same bytes, no device."""
+    fn = _container_sym("rh_deflate_blocks_host", C.c_int, _DEFLATE_LEAD + _DEFLATE_TAIL)
+    return _deflate_call(fn, data, start, end, strategy, ())
+
+
+def deflate_bound(n: int) -> int:
+    """rh_deflate_bound: the largest size a stream for n bytes can take."""
+    return int(_container_sym("rh_deflate_bound", C.c_uint64, [C.c_uint64])(n))
+
+
+def deflate_last() -> dict:
+    """rh_deflate_last: the most recent device deflate of this process -- GPU time of its two kernels, bytes in and out."""
+    fn = _container_sym("rh_deflate_last", None, [C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)])
+    a, b, c, d = C.c_float(), C.c_float(), C.c_uint64(), C.c_uint64()
+    fn(C.byref(a), C.byref(b), C.byref(c), C.byref(d))
+    return {"deflate_ms": a.value, "gather_ms": b.value, "in_bytes": c.value, "out_bytes": d.value}
+
+
 # Tolerant container reads (DESIGN.md 14.2): added like the entry points above, looked up by symbol.
 BLOCK_END, BLOCK_DROPPED, BLOCK_COUNT, BLOCK_TOO_LARGE, BLOCK_INFLATE = 0x100, 0x200, 0x201, 0x202, 0x300
 BLOCK_STATUS = np.dtype([("code", np.uint32), ("aux", np.uint32), ("detail", np.int64), ("kept", np.uint64)])

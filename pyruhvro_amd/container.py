@@ -12,6 +12,8 @@ their offsets; the ordinary decode then runs on them.  ``columns=`` and ``reader
 either here with ``zlib``, block by block, into one buffer (``inflate="host"``, the default), or on the device: the
 compressed file is uploaded as it is and two kernels inflate its blocks, one wavefront per block (``inflate="device"``, or
 ``RUHVRO_HIP_INFLATE=device`` in the environment).  Both roads accept the same streams and raise the same messages.
+``write_container(..., codec="deflate", deflate="device")`` (or ``RUHVRO_HIP_DEFLATE=device``) compresses the blocks on the
+device as well, 32 KiB segments in parallel; the default ``"host"`` is ``zlib`` on the calling thread.
 
     batches, errors = pyruhvro.read_container_tolerant("events.avro", 8)   # what a damaged file still holds, and what it lost
 
@@ -290,13 +292,27 @@ def _put_bytes(out: bytearray, b: bytes) -> None:
     out += b
 
 
-def write_container(batch, schema, *, codec: str = "null", block_rows: int = 4096, sync: Optional[bytes] = None, metadata=None) -> bytes:
+def _deflate_road(deflate) -> str:
+    """``deflate=`` of a write: "host" or "device"; None reads RUHVRO_HIP_DEFLATE (per call) and falls back to "host"."""
+    if deflate is None:
+        deflate = os.environ.get("RUHVRO_HIP_DEFLATE") or "host"
+    if deflate not in ("host", "device"):
+        raise ValueError("container: deflate must be 'host' or 'device'")
+    return deflate
+
+
+def write_container(batch, schema, *, codec: str = "null", block_rows: int = 4096, sync: Optional[bytes] = None, metadata=None,
+                    deflate=None) -> bytes:
     """Extension.  ``batch`` (a ``pyarrow.RecordBatch``) as an Avro object container: host framing around
     ``serialize_record_batch`` (the GPU encoder).  One block per ``block_rows`` rows; the header carries ``schema`` verbatim,
     the codec (``"null"`` or ``"deflate"``) and the caller's ``metadata`` (``{str: bytes or str}``; the ``avro.`` names are the
-    format's own).  ``sync``: the 16-byte marker, random by default."""
+    format's own).  ``sync``: the 16-byte marker, random by default.  ``deflate``: where a ``deflate`` file's blocks are
+    compressed -- ``"host"`` (``zlib``, block by block on the calling thread), ``"device"`` (the GPU: every block in one call,
+    32 KiB segments in parallel; raw RFC 1951 streams any inflater reads, not the bytes ``zlib`` would write), ``None`` =
+    ``RUHVRO_HIP_DEFLATE`` or ``"host"``."""
     import numpy as np
     import pyruhvro_amd as P
+    road = _deflate_road(deflate)                                # ValueError before any device work, for codec="null" too
     if not isinstance(schema, str):
         raise TypeError("argument 'schema': expected str")
     if codec not in ("null", "deflate"):
@@ -341,10 +357,18 @@ def write_container(batch, schema, *, codec: str = "null", block_rows: int = 409
         bufs = records.buffers()
         offs = np.frombuffer(bufs[1], dtype=off_t, count=records.offset + n + 1)[records.offset:]
         data = memoryview(bufs[2]) if bufs[2] is not None else memoryview(b"")
-        for r0 in range(0, n, block_rows):
+        if codec == "deflate" and road == "device":              # every block's payload in one call; zlib is not called
+            from . import cabi
+            edges = offs[np.append(np.arange(0, n, block_rows), n)].astype(np.uint64)
+            raw = np.frombuffer(data, dtype=np.uint8) if data.nbytes else np.zeros(0, dtype=np.uint8)
+            blob, c_start, c_end = cabi.deflate_blocks(raw, edges[:-1], edges[1:])
+            blob = memoryview(blob)
+        for b, r0 in enumerate(range(0, n, block_rows)):
             r1 = min(r0 + block_rows, n)
             payload = data[int(offs[r0]):int(offs[r1])]
-            if codec == "deflate":
+            if codec == "deflate" and road == "device":
+                payload = blob[int(c_start[b]):int(c_end[b])]
+            elif codec == "deflate":
                 c = zlib.compressobj(wbits=-15)
                 payload = c.compress(payload) + c.flush()
             _put_long(out, r1 - r0)

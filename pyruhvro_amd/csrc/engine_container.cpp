@@ -1,10 +1,13 @@
 // Avro object container files: the framing scan behind the C ABI (rh_container_scan: host only) and the
 // blocks entry points (rh_decode_blocks / rh_decode_blocks_device): the file uploaded as it is, rh_k_split (container.hip)
 // turning the block table into record offsets, then the device-input decode (decode_device_impl) on (d_data, d_offsets, n).
+// Deflate blocks in both directions: rh_decode_cblocks / rh_inflate_blocks (inflate.hip) and rh_deflate_blocks
+// with its host twin (deflate.hip, deflate_core.h).
 #include "engine_internal.h"
 #include "container.h"
 #include "container_scan.h"
 #include "inflate.h"
+#include "deflate.h"
 
 extern "C" {
 uint32_t rh_split_lds_bytes(int list_depth);
@@ -13,6 +16,8 @@ int rh_launch_split_salvage(const rh::SalvageParams* P, void* stream);
 int rh_launch_salvage_gather(const rh::SalvageGatherParams* G, void* stream);
 int rh_launch_inflate_size(const rh::InflateParams* P, void* stream);
 int rh_launch_inflate_emit(const rh::InflateParams* P, void* stream);
+int rh_launch_deflate(const rh::DeflateParams* P, void* stream);
+int rh_launch_deflate_gather(const rh::DeflateGatherParams* P, void* stream);
 }
 
 using namespace rhe;
@@ -309,6 +314,105 @@ static uint64_t block_limit_of(uint64_t max_block_bytes) { return max_block_byte
 static void check_compressed_table(const uint64_t* start, const uint64_t* end, uint64_t nb, uint64_t len) {
   for (uint64_t b = 0; b < nb; b++)
     if (start[b] > end[b] || end[b] > len || (b && start[b] < end[b - 1])) throw std::invalid_argument(block_where(b) + "its bytes are outside the buffer or out of order");
+}
+
+// ---- deflate blocks written on the device (deflate.hip) ----------------------------------------------------------
+static_assert(RH_DEFLATE_AUTO == rhd::AUTO && RH_DEFLATE_STORED == rhd::STORED && RH_DEFLATE_FIXED == rhd::FIXED && RH_DEFLATE_DYNAMIC == rhd::DYNAMIC,
+              "RH_DEFLATE_* are the strategies of deflate_core.h");
+static std::mutex g_deflate_last_mu;
+static struct { float deflate_ms = 0, gather_ms = 0; uint64_t in_bytes = 0, out_bytes = 0; } g_deflate_last;
+
+// What both deflate calls refuse before anything else.
+static void check_deflate_call(const uint8_t* data, uint64_t len, const uint64_t* start, const uint64_t* end, uint64_t nb, uint32_t strategy) {
+  if (nb > 0xFFFFFFFFull) throw std::invalid_argument("container: more than 2^32 - 1 blocks");
+  if (nb && (!start || !end || !data)) throw std::invalid_argument("container: null block table");
+  if (strategy > rhd::DYNAMIC) throw std::invalid_argument("container: deflate strategy " + std::to_string(strategy) + " is not one of 0 .. 3");
+  check_compressed_table(start, end, nb, len);
+  for (uint64_t b = 0; b < nb; b++)
+    if (block_too_large(end[b] - start[b])) throw std::invalid_argument(block_large_message(b, end[b] - start[b]));
+}
+
+// The two kernels around their one synchronisation: the payloads and the segment table go up, rh_k_deflate fills the slots, the
+// sizes come back and are prefix-summed here, rh_k_deflate_gather packs the streams, and the compressed bytes come down.
+static void deflate_on_device(const uint8_t* data, uint64_t len, const uint64_t* start, const uint64_t* end, uint64_t nb, uint32_t strategy, int device,
+                              hipStream_t stream, std::unique_ptr<uint8_t, void (*)(void*)>& host, uint64_t* out_len, uint64_t* out_start, uint64_t* out_end) {
+  std::vector<uint64_t> seg_in, slot;
+  std::vector<uint32_t> seg_len;
+  uint64_t scratch_len = 0, in_bytes = 0;
+  for (uint64_t b = 0; b < nb; b++) {
+    const uint64_t size = end[b] - start[b], k = rhd::segments_of(size);
+    in_bytes += size;
+    for (uint64_t j = 0; j < k; j++) {
+      const uint64_t at = j * rhd::kSegment, n = size - at < rhd::kSegment ? size - at : rhd::kSegment;
+      const bool last = j + 1 == k;
+      seg_in.push_back(start[b] + at);
+      seg_len.push_back((uint32_t)n | (last ? rh::kSegLast : 0u));
+      slot.push_back(scratch_len);
+      scratch_len += (rhd::segment_bound(n, last) + 15) & ~15ull;
+    }
+  }
+  const uint64_t ns = seg_in.size();
+  if (ns > 0xFFFFFFFFull) throw std::invalid_argument("container: more than 2^32 - 1 deflate segments");
+  Lease d_data(dev_pool(), len + 64, device), d_scratch(dev_pool(), scratch_len + 64, device);
+  if (len) HIPCHK(hipMemcpyAsync(d_data.ptr(), data, len, hipMemcpyHostToDevice, stream));
+  // seg_in[ns], slot[ns], out_at[ns], seg_len[ns], seg_size[ns], bad
+  const uint64_t o_slot = 8 * ns, o_at = 16 * ns, o_len = 24 * ns, o_size = 28 * ns, o_bad = (32 * ns + 7) & ~7ull;
+  Lease d_tab(dev_pool(), o_bad + 8, device);
+  if (ns) {
+    HIPCHK(hipMemcpyAsync(d_tab.ptr(), seg_in.data(), 8 * ns, hipMemcpyHostToDevice, stream));
+    HIPCHK(hipMemcpyAsync(d_tab.ptr() + o_slot, slot.data(), 8 * ns, hipMemcpyHostToDevice, stream));
+    HIPCHK(hipMemcpyAsync(d_tab.ptr() + o_len, seg_len.data(), 4 * ns, hipMemcpyHostToDevice, stream));
+  }
+  HIPCHK(hipMemsetAsync(d_tab.ptr() + o_size, 0, o_bad + 8 - o_size, stream));
+  unsigned long long* d_bad = (unsigned long long*)(d_tab.ptr() + o_bad);
+  rh::DeflateParams P;
+  std::memset(&P, 0, sizeof P);
+  P.data = d_data.ptr(); P.data_len = len;
+  P.seg_in = (const uint64_t*)d_tab.ptr(); P.seg_len = (const uint32_t*)(d_tab.ptr() + o_len); P.slot = (const uint64_t*)(d_tab.ptr() + o_slot);
+  P.scratch = d_scratch.ptr(); P.scratch_len = scratch_len;
+  P.seg_size = (uint32_t*)(d_tab.ptr() + o_size);
+  P.ns = (uint32_t)ns; P.strategy = strategy; P.bad = d_bad;
+  Events ev;
+  ev.init();
+  ev.rec(0, stream);
+  if (rh_launch_deflate(&P, stream)) throw HipError("k_deflate launch failed");
+  ev.rec(1, stream);
+  std::vector<uint32_t> seg_size(ns, 0);
+  unsigned long long bad = 0;
+  if (ns) HIPCHK(hipMemcpyAsync(seg_size.data(), P.seg_size, 4 * ns, hipMemcpyDeviceToHost, stream));
+  HIPCHK(hipMemcpyAsync(&bad, d_bad, 8, hipMemcpyDeviceToHost, stream));
+  HIPCHK(hipStreamSynchronize(stream));      // the one synchronisation: the host needs the total to lease the output
+  if (bad) throw std::runtime_error("internal error: the deflate kernel refused segment " + std::to_string(~bad));
+  d_data.release();
+  std::vector<uint64_t> out_at(ns, 0);
+  uint64_t total = 0, s = 0;
+  for (uint64_t b = 0; b < nb; b++) {
+    out_start[b] = total;
+    for (uint64_t k = rhd::segments_of(end[b] - start[b]); k; k--, s++) {
+      out_at[s] = total;
+      total += seg_size[s];
+    }
+    out_end[b] = total;
+  }
+  Lease d_out(dev_pool(), total + 64, device);
+  if (ns) HIPCHK(hipMemcpyAsync(d_tab.ptr() + o_at, out_at.data(), 8 * ns, hipMemcpyHostToDevice, stream));
+  rh::DeflateGatherParams G;
+  std::memset(&G, 0, sizeof G);
+  G.scratch = d_scratch.ptr(); G.scratch_len = scratch_len;
+  G.slot = P.slot; G.seg_size = P.seg_size; G.out_at = (const uint64_t*)(d_tab.ptr() + o_at);
+  G.out = d_out.ptr(); G.out_len = total; G.ns = (uint32_t)ns; G.bad = d_bad;
+  ev.rec(2, stream);
+  if (rh_launch_deflate_gather(&G, stream)) throw HipError("k_deflate_gather launch failed");
+  ev.rec(3, stream);
+  host.reset((uint8_t*)std::malloc(total ? total : 1));
+  if (!host) throw std::bad_alloc();
+  if (total) HIPCHK(hipMemcpyAsync(host.get(), d_out.ptr(), total, hipMemcpyDeviceToHost, stream));
+  HIPCHK(hipMemcpyAsync(&bad, d_bad, 8, hipMemcpyDeviceToHost, stream));
+  HIPCHK(hipStreamSynchronize(stream));
+  if (bad) throw std::runtime_error("internal error: the deflate gather kernel refused segment " + std::to_string(~bad));
+  *out_len = total;
+  std::lock_guard<std::mutex> g(g_deflate_last_mu);
+  g_deflate_last.deflate_ms = ev.ms(0, 1); g_deflate_last.gather_ms = ev.ms(2, 3); g_deflate_last.in_bytes = in_bytes; g_deflate_last.out_bytes = total;
 }
 
 static rh_device_result* decode_cblocks_impl(rh_schema* s, const uint8_t* data, uint64_t len, const uint64_t* start, const uint64_t* end,
@@ -829,6 +933,63 @@ void rh_inflate_last(float* size_ms, float* emit_ms, uint64_t* in_bytes, uint64_
   if (emit_ms) *emit_ms = g_inflate_last.emit_ms;
   if (in_bytes) *in_bytes = g_inflate_last.in_bytes;
   if (out_bytes) *out_bytes = g_inflate_last.out_bytes;
+}
+
+int rh_deflate_blocks(const uint8_t* data, uint64_t len, const uint64_t* start, const uint64_t* end, uint64_t nb, uint32_t strategy,
+                      const rh_opts* opts, uint8_t** out, uint64_t* out_len, uint64_t* out_start, uint64_t* out_end, char** err) {
+  if (!out || !out_len || (nb && (!out_start || !out_end))) return RH_ERR_ARGUMENT;
+  *out = nullptr;
+  *out_len = 0;
+  return guarded(err, [&] {
+    if (opts && opts->n_devices > 0) throw std::invalid_argument("container: a container is written on one device (rh_opts.devices is refused)");
+    if (opts && (opts->flags & RH_ASYNC)) throw std::invalid_argument("container: the blocks call is synchronous: RH_ASYNC is refused");
+    check_deflate_call(data, len, start, end, nb, strategy);
+    require_device();
+    int device = 0;
+    if (opts && opts->device >= 0) { HIPCHK(hipSetDevice(opts->device)); device = opts->device; }
+    else HIPCHK(hipGetDevice(&device));
+    hipStream_t stream = opts ? (hipStream_t)opts->stream : nullptr;
+    std::unique_ptr<uint8_t, void (*)(void*)> host(nullptr, std::free);
+    deflate_on_device(data, len, start, end, nb, strategy, device, stream, host, out_len, out_start, out_end);
+    *out = host.release();
+    return RH_OK;
+  });
+}
+
+int rh_deflate_blocks_host(const uint8_t* data, uint64_t len, const uint64_t* start, const uint64_t* end, uint64_t nb, uint32_t strategy,
+                           uint8_t** out, uint64_t* out_len, uint64_t* out_start, uint64_t* out_end, char** err) {
+  if (!out || !out_len || (nb && (!out_start || !out_end))) return RH_ERR_ARGUMENT;
+  *out = nullptr;
+  *out_len = 0;
+  return guarded(err, [&] {
+    check_deflate_call(data, len, start, end, nb, strategy);
+    uint64_t room = 0;
+    for (uint64_t b = 0; b < nb; b++) room += rhd::deflate_bound(end[b] - start[b]);
+    std::unique_ptr<uint8_t, void (*)(void*)> host((uint8_t*)std::malloc(room ? room : 1), std::free);
+    if (!host) throw std::bad_alloc();
+    std::unique_ptr<rhd::State> S(new rhd::State);
+    uint64_t total = 0;
+    for (uint64_t b = 0; b < nb; b++) {
+      const uint64_t size = rhd::deflate_stream_host(*S, data + start[b], end[b] - start[b], strategy, host.get() + total);
+      if (size == ~0ull) throw std::runtime_error("internal error: the deflate writer passed the bound of block " + std::to_string(b));
+      out_start[b] = total;
+      total += size;
+      out_end[b] = total;
+    }
+    *out = host.release();
+    *out_len = total;
+    return RH_OK;
+  });
+}
+
+uint64_t rh_deflate_bound(uint64_t len) { return rhd::deflate_bound(len); }
+
+void rh_deflate_last(float* deflate_ms, float* gather_ms, uint64_t* in_bytes, uint64_t* out_bytes) {
+  std::lock_guard<std::mutex> g(g_deflate_last_mu);
+  if (deflate_ms) *deflate_ms = g_deflate_last.deflate_ms;
+  if (gather_ms) *gather_ms = g_deflate_last.gather_ms;
+  if (in_bytes) *in_bytes = g_deflate_last.in_bytes;
+  if (out_bytes) *out_bytes = g_deflate_last.out_bytes;
 }
 
 }  // extern "C"

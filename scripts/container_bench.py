@@ -18,6 +18,10 @@ inflate kernels' GPU times (rh_inflate_last) and the split's beside them -> prof
 ~64 KB blocks read by read_container, the same clean file by read_container_tolerant, and the same file with 1 % of its blocks
 damaged (12 bytes of 0xFF in the middle of the payload) by read_container_tolerant; medians of `--reps` (default 5) with min and
 max, the salvage's own kernel times (rh_salvage_last) beside them -> profiles/container_salvage_10m.json.  No threshold.
+`--deflate` measures instead the two roads of a `deflate` WRITE: the records as one RecordBatch written by
+write_container(codec="deflate") at block_rows 512 and 4096, deflate="host" and deflate="device" alternated in one job, medians of 3
+after one warm call of each, with the two deflate kernels' GPU times (rh_deflate_last) and both roads' file sizes
+-> profiles/container_deflate_10m.json.  No threshold: the yardstick is the host row of the same job.
 One JSON object on stdout, also written to --out; the Markdown table on stderr and into DESIGN.md 14, between its two marker
 lines (--design '' leaves the document alone; --from-json FILE rewrites the table from an earlier run's JSON without measuring).
 """
@@ -165,6 +169,71 @@ def inflate_rows(a) -> int:
     return 0
 
 
+def deflate_rows(a) -> int:
+    """The two roads of a deflate write, alternated: the yardstick is the host row of the same job."""
+    import numpy as np
+    import pyarrow as pa
+    import torch  # noqa: F401  first: the engine shares torch's HIP runtime
+    from avrogen import fastgen
+    from avrogen.schemas import SCHEMAS
+    import pyruhvro_amd as P
+    from pyruhvro_amd import cabi
+
+    t_start = time.perf_counter()
+
+    def note(what):
+        print(f"[{time.perf_counter() - t_start:6.1f} s] {what}", file=sys.stderr, flush=True)
+
+    schema = SCHEMAS["full"]
+    note(f"generating {a.records} records")
+    data, offsets = fastgen.generate("full", a.records)
+    old = P.set_kernel_mode("specialized")
+    arr = pa.LargeBinaryArray.from_buffers(pa.large_binary(), a.records, [None, pa.py_buffer(offsets.view(np.int64)), pa.py_buffer(data)])
+    batch = P.deserialize_binary_array(arr, schema, 1)[0]
+    del arr, data
+    note(f"one batch of {batch.num_rows} rows")
+    reps = 3
+    out = {"workload": "full", "records": a.records, "payload_bytes": int(offsets[-1]), "reps": reps, "codec": "deflate", "rows": {}}
+    for block_rows in (512, 4096):
+        label = f"block_rows_{block_rows}"
+        walls = {"host": [], "device": []}
+        kern, sizes = [], {}
+        for rep in range(-1, reps):      # (rep -1: both roads once, warm, and read back)
+            for road in ("host", "device"):
+                t0 = time.perf_counter()
+                blob = P.write_container(batch, schema, codec="deflate", block_rows=block_rows, sync=SYNC, deflate=road)
+                ms = (time.perf_counter() - t0) * 1e3
+                note(f"{label}: {road} {ms:.0f} ms, {len(blob)} bytes")
+                if rep < 0:
+                    sizes[road] = len(blob)
+                    back = P.read_container(blob, 1, inflate="device")
+                    assert len(back) == 1 and back[0].equals(batch), f"{label}: the {road} road's file does not read back"
+                    del back
+                else:
+                    walls[road].append(ms)
+                    if road == "device":
+                        kern.append(cabi.deflate_last())
+                del blob
+        row = {"blocks": -(-a.records // block_rows)}
+        for road in ("host", "device"):
+            w = walls[road]
+            row[road] = {"wall_ms": statistics.median(w), "wall_ms_min": min(w), "wall_ms_max": max(w), "file_bytes": sizes[road]}
+        row["device"].update({"deflate_kernel_ms": statistics.median(k["deflate_ms"] for k in kern),
+                              "gather_kernel_ms": statistics.median(k["gather_ms"] for k in kern),
+                              "in_bytes": kern[0]["in_bytes"], "out_bytes": kern[0]["out_bytes"]})
+        row["device_over_host"] = row["device"]["wall_ms"] / row["host"]["wall_ms"]
+        row["device_file_over_host_file"] = sizes["device"] / sizes["host"]
+        out["rows"][label] = row
+    P.set_kernel_mode(old)
+    note("done")
+    text = json.dumps(out, indent=1)
+    print(text)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        open(a.out, "w").write(text + "\n")
+    return 0
+
+
 def tolerant_rows(a) -> int:
     """Strict, tolerant on the clean file, tolerant on the damaged file: alternated, the yardstick is the strict row of the same job."""
     import numpy as np
@@ -242,6 +311,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--tolerant", action="store_true", help="the strict and the tolerant read of a clean and of a damaged file (see above); --out defaults to profiles/container_salvage_10m.json")
     ap.add_argument("--inflate", action="store_true", help="the host and the device road of a deflate file (see above); --out defaults to profiles/container_inflate_10m.json")
+    ap.add_argument("--deflate", action="store_true", help="the host and the device road of a deflate write (see above); --out defaults to profiles/container_deflate_10m.json")
     ap.add_argument("--design", default=os.path.join(ROOT, "DESIGN.md"), help="the document whose table is rewritten ('' = none)")
     ap.add_argument("--from-json", default=None, help="no measurement: the table of an earlier run's JSON")
     ap.add_argument("--records", type=int, default=10_000_000)
@@ -258,6 +328,10 @@ def main():
         if a.out == ap.get_default("out"):
             a.out = os.path.join(ROOT, "profiles", "container_inflate_10m.json")
         return inflate_rows(a)
+    if a.deflate:
+        if a.out == ap.get_default("out"):
+            a.out = os.path.join(ROOT, "profiles", "container_deflate_10m.json")
+        return deflate_rows(a)
     if a.from_json:
         report(json.load(open(a.from_json)), a.design)
         return 0
