@@ -567,6 +567,66 @@ int rh_decode_blocks_tolerant_device(const rh_schema* s, const uint8_t* data, ui
  * reported (extra_errors not among them), the bytes it gathered (0 = the buffer was decoded where it was). */
 void rh_salvage_last(float* split_ms, float* gather_ms, uint64_t* blocks_reported, uint64_t* bytes_gathered);
 
+/* Row filters.  Added WITHOUT a change of RH_ABI_VERSION (7), discovered by symbol.
+ *
+ * A filtered strict decode returns, buffer for buffer, the strict decode of the records whose values match a predicate -- the
+ * records are chosen on the device, from the raw bytes, before anything is decoded.  A predicate is 1 to 8 terms, ANDed; a term
+ * names a top-level field of the WRITER schema (whether or not the call's projection or reader schema builds it), an operator
+ * ("==" "!=" "<" "<=" ">" ">=" "is_null" "not_null") and a value.  Fields: int / long and their logical types (int64 order),
+ * float / double (the value widened to double, IEEE order: NaN fails everything but "!=", -0.0 == 0.0), boolean and enum ("==" /
+ * "!=" only; an enum against one of its symbol names), string / bytes (unsigned bytewise order, a proper prefix first, at most
+ * 255 comparand bytes); plain or in a union with null, either order.  A null value fails every comparison, "!=" included; on a
+ * field that cannot be null "is_null" keeps nothing and "not_null" everything.
+ * rh_filter_compile refuses, with RH_ERR_SCHEMA and a message that starts with "where: " and names the field: an unknown field or
+ * a dotted path, a field of any other kind ("not supported yet"), an operator the kind does not take, a value of the wrong kind or
+ * out of range, an unknown enum symbol, a comparand over 255 bytes, zero terms or more than 8.  `writer` is a schema of
+ * rh_schema_compile: a projected or resolved one is RH_ERR_ARGUMENT.  The filter is immutable and does not reference `writer`.
+ * Every record is walked in full with the strict decode's checks: a malformed record fails the call with the strict decode's
+ * message for the lowest failing record of the WHOLE list (RH_ERR_DECODE), whatever the predicate says about it.
+ * rh_filter_packed / rh_filter_device: the kernel alone -- bit i of keep_words[i / 64] (room for ceil(n / 64) words, host memory)
+ * says whether record i is kept, *kept how many are.
+ * rh_decode_where / rh_decode_packed_where / rh_decode_device_where: rh_decode / rh_decode_packed / rh_decode_device with the
+ * filter -- `s` plain, projected or resolved, made from the writer schema the filter was compiled against (else
+ * RH_ERR_ARGUMENT).  num_chunks applies to the kept records (out_chunks: room for rh_clamp_chunks(n, num_chunks) always suffices);
+ * nothing kept gives what a decode of no records gives.  A call that keeps every record decodes its input where it is; otherwise
+ * the kept records are gathered into a device buffer the result owns.  The host forms upload the list in one piece (not the
+ * pinned, pipelined path of rh_decode).  One device: rh_opts.devices and RH_ASYNC are refused with RH_ERR_ARGUMENT.
+ * rh_filter_last: GPU time of the most recent call's filter kernel and of its compaction (offsets + gather; 0 = none ran), the
+ * records it was given and the records it kept. */
+typedef struct rh_filter rh_filter;
+#define RH_FILTER_VALUE_NONE 0     /* is_null / not_null                                                       */
+#define RH_FILTER_VALUE_INT 1      /* i, and the same value in d                                               */
+#define RH_FILTER_VALUE_DOUBLE 2   /* d                                                                        */
+#define RH_FILTER_VALUE_BOOL 3     /* i = 0 / 1                                                                */
+#define RH_FILTER_VALUE_BYTES 4    /* bytes[0 .. len): UTF-8 text or raw bytes, an enum symbol's name           */
+#define RH_FILTER_VALUE_BIGINT 5   /* an integer outside the int64 range: d holds it (refused for int / long)   */
+typedef struct rh_filter_term {
+  const char* name;
+  const char* op;
+  int32_t value_kind;
+  int32_t reserved;
+  int64_t i;
+  double d;
+  const uint8_t* bytes;
+  uint64_t len;
+} rh_filter_term;
+int rh_filter_compile(const rh_schema* writer, const rh_filter_term* terms, uint32_t n, rh_filter** out, char** err);
+void rh_filter_free(rh_filter* f);
+int rh_filter_packed(const rh_filter* f, const uint8_t* data, const uint64_t* offsets, uint64_t n, const rh_opts* opts,
+                     uint64_t* keep_words, uint64_t* kept, char** err);
+int rh_filter_device(const rh_filter* f, const void* d_data, const void* d_offsets, uint64_t data_len, uint64_t n, const rh_opts* opts,
+                     uint64_t* keep_words, uint64_t* kept, char** err);
+int rh_decode_where(const rh_schema* s, const uint8_t* const* ptrs, const uint64_t* lens, uint64_t n, uint64_t num_chunks,
+                    const rh_opts* opts, struct ArrowArray* out_chunks, uint32_t* out_k, rh_stats* stats, char** err,
+                    const rh_filter* filter, uint64_t* kept);
+int rh_decode_packed_where(const rh_schema* s, const uint8_t* data, const uint64_t* offsets, uint64_t n, uint64_t num_chunks,
+                           const rh_opts* opts, struct ArrowArray* out_chunks, uint32_t* out_k, rh_stats* stats, char** err,
+                           const rh_filter* filter, uint64_t* kept);
+int rh_decode_device_where(const rh_schema* s, const void* d_data, const void* d_offsets, uint64_t data_len, uint64_t n,
+                           uint64_t num_chunks, const rh_opts* opts, rh_device_result** out, rh_stats* stats, char** err,
+                           const rh_filter* filter, uint64_t* kept);
+void rh_filter_last(float* filter_ms, float* gather_ms, uint64_t* n, uint64_t* kept);
+
 /* Measurement hook, not part of the drop-in surface: the host-side gather of a `shards`-GPU rh_decode call (every shard's
  * record slices copied into its staging buffer by its own host thread + `threads_per_shard` helpers, all shards at once)
  * without the GPUs -- pageable destinations (pinned = 0, runs on a box with no device), pinned ones (1), or pageable ones placed

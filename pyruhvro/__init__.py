@@ -2,7 +2,8 @@
 
 Same five functions as the reference's PyO3 module (src/lib.rs:150-158); the three decode functions also take the
 keyword-only extensions ``columns=[...]`` (decode only those top-level fields) and ``reader_schema=`` (decode
-writer-encoded records into an evolved schema).  Beside them the tolerant decode: the
+writer-encoded records into an evolved schema) and ``where=`` (decode only the records that match a predicate;
+``filter_records`` is that filter alone).  Beside them the tolerant decode: the
 ``*_tolerant`` functions replace malformed records by ``placeholder_datum(schema)`` and report all of them; and the Avro
 object container files: ``container_info`` / ``read_container`` / ``read_container_to_device`` / ``write_container``, and
 ``read_container_tolerant`` / ``read_container_to_device_tolerant``, which salvage what a damaged file still holds."""
@@ -20,6 +21,7 @@ from pyruhvro_amd import (  # noqa: F401
     deserialize_to_device,
     placeholder_datum,
     validate_records,
+    filter_records,
     deserialize_array,
     deserialize_array_threaded,
     deserialize_array_threaded_spawn,

@@ -154,8 +154,23 @@ def _current_devices():
     return _devices if _devices is not None else _env_devices()
 
 
+def _decode_where(list_, schema: str, num_chunks: int, columns, reader_schema, where):
+    """The filtered strict decode: the list packed on the host and uploaded in one piece (rh_decode_packed_where; not the pinned,
+    pipelined list path of the unfiltered call)."""
+    from . import cabi
+    cabi.check_where(where)                    # TypeError / ValueError before any native work
+    _get_schema(schema, columns, reader_schema)
+    _check_chunks(num_chunks)
+    cabi.Filter.get(schema, where)             # ValueError "where: ..." before the list is touched
+    data, offs = _pack_records(list_)
+    return cabi.decode_packed(data, offs, schema, num_chunks, kernel=_kernel_mode, devices=_current_devices(), columns=columns,
+                              reader_schema=reader_schema, where=where)
+
+
 def _decode(list_, schema: str, num_chunks: int, want_stats: bool = False, device: int = -1, stream: int = 0, columns=None,
-            reader_schema=None):
+            reader_schema=None, where=None):
+    if where is not None:
+        return _decode_where(list_, schema, num_chunks, columns, reader_schema, where), None
     comp = _get_schema(schema, columns, reader_schema)
     nat = _require_native()
     if not isinstance(num_chunks, int) or isinstance(num_chunks, bool):
@@ -177,7 +192,7 @@ def _decode(list_, schema: str, num_chunks: int, want_stats: bool = False, devic
     return out, stats
 
 
-def deserialize_array(list, schema, *, columns=None, reader_schema=None):  # noqa: A002 - the reference's parameter name
+def deserialize_array(list, schema, *, columns=None, reader_schema=None, where=None):  # noqa: A002 - the reference's parameter name
     """src/lib.rs:56-71 -> ruhvro::deserialize::per_datum_deserialize (deserialize.rs:25-30).
 
     ``columns`` (keyword only, an extension): decode only these top-level fields, in this order -- the batch equals the
@@ -187,19 +202,27 @@ def deserialize_array(list, schema, *, columns=None, reader_schema=None):  # noq
     ``reader_schema`` (keyword only, an extension): ``schema`` is the schema the records were WRITTEN with and the batch is
     in this Avro schema -- fields matched by name, writer fields it lacks dropped, fields the writer lacks filled with their
     ``default``, columns in its order, int / long / float promoted, string <-> bytes (DESIGN.md 13 for the rules and what is
-    refused, with a ``ValueError`` that starts with ``reader schema:``).  ``columns`` then names reader fields."""
-    return _decode(list, schema, 1, columns=columns, reader_schema=reader_schema)[0][0]
+    refused, with a ``ValueError`` that starts with ``reader schema:``).  ``columns`` then names reader fields.
+
+    ``where`` (keyword only, an extension): decode only the records that match a predicate -- one term ``(name, op, value)`` or a
+    list of up to 8 terms, ANDed; ``op`` is one of ``== != < <= > >= is_null not_null``; ``name`` is a top-level field of the
+    WRITER schema, whether or not ``columns`` / ``reader_schema`` build it.  The batch equals the decode of the matching
+    records alone, buffer for buffer; the records are chosen on the GPU before anything is decoded.  A null matches no
+    comparison.  A malformed record raises the plain decode's error, whatever the predicate says about it (DESIGN.md 15
+    for the field kinds and what is refused, with a ``ValueError`` that starts with ``where:``)."""
+    return _decode(list, schema, 1, columns=columns, reader_schema=reader_schema, where=where)[0][0]
 
 
-def deserialize_array_threaded(list, schema, num_chunks, *, columns=None, reader_schema=None):  # noqa: A002
+def deserialize_array_threaded(list, schema, num_chunks, *, columns=None, reader_schema=None, where=None):  # noqa: A002
     """src/lib.rs:73-89 -> per_datum_deserialize_threaded (deserialize.rs:76-121):
-    ``clamp(num_chunks, 1, max(len(list), 1))`` batches, chunk order preserved.  ``columns`` / ``reader_schema``: see deserialize_array."""
-    return _decode(list, schema, num_chunks, columns=columns, reader_schema=reader_schema)[0]
+    ``clamp(num_chunks, 1, max(len(list), 1))`` batches, chunk order preserved.  ``columns`` / ``reader_schema`` / ``where``: see
+    deserialize_array (the chunking applies to the records ``where`` keeps)."""
+    return _decode(list, schema, num_chunks, columns=columns, reader_schema=reader_schema, where=where)[0]
 
 
-def deserialize_array_threaded_spawn(list, schema, num_chunks, *, columns=None, reader_schema=None):  # noqa: A002
+def deserialize_array_threaded_spawn(list, schema, num_chunks, *, columns=None, reader_schema=None, where=None):  # noqa: A002
     """src/lib.rs:108-128 -- same results as deserialize_array_threaded (deserialize.rs:127-170)."""
-    return _decode(list, schema, num_chunks, columns=columns, reader_schema=reader_schema)[0]
+    return _decode(list, schema, num_chunks, columns=columns, reader_schema=reader_schema, where=where)[0]
 
 
 def deserialize_array_threaded_with_stats(list, schema, num_chunks, device: int = -1, *, columns=None, reader_schema=None):  # noqa: A002
@@ -214,13 +237,15 @@ def last_decode_profile():
     return _native.last_decode_profile()
 
 
-def deserialize_binary_array(array, schema, num_chunks, *, columns=None, reader_schema=None):
+def deserialize_binary_array(array, schema, num_chunks, *, columns=None, reader_schema=None, where=None):
     """Extension: the same decode for records that already sit in an Arrow
     ``BinaryArray`` / ``LargeBinaryArray`` (one record per element) -- the form the reference packs its
     list into internally (deserialize.rs:90).  Zero-copy on the payload: no per-``bytes`` extraction
-    under the GIL.  Returns ``list[pyarrow.RecordBatch]`` with the chunking of deserialize_array_threaded."""
+    under the GIL.  Returns ``list[pyarrow.RecordBatch]`` with the chunking of deserialize_array_threaded.  ``where``: see
+    deserialize_array."""
     import numpy as np
     from . import cabi
+    cabi.check_where(where)
     if isinstance(array, pa.ChunkedArray):
         array = array.combine_chunks() if array.num_chunks != 1 else array.chunk(0)
     if not isinstance(array, (pa.BinaryArray, pa.LargeBinaryArray)):
@@ -242,7 +267,7 @@ def deserialize_binary_array(array, schema, num_chunks, *, columns=None, reader_
             else np.zeros(1, dtype=np.uint8))
     offsets = (offs.astype(np.uint64) - np.uint64(base)) if n else np.zeros(1, dtype=np.uint64)
     return cabi.decode_packed(data, offsets, schema, num_chunks, kernel=_kernel_mode, devices=_current_devices(), columns=columns,
-                              reader_schema=reader_schema)
+                              reader_schema=reader_schema, where=where)
 
 
 def _check_chunks(num_chunks):
@@ -281,6 +306,18 @@ def validate_records(list, schema, *, max_errors=1024, reader_schema=None):  # n
     _get_schema(schema)
     data, offs = _pack_records(list)
     return cabi.validate_packed(data, offs, schema, check_max_errors(max_errors), devices=_current_devices())
+
+
+def filter_records(list, schema, where):  # noqa: A002
+    """Extension.  The row filter alone (see ``deserialize_array``'s ``where``): a numpy ``bool[len(list)]``, True where the record
+    matches.  A malformed record raises what ``deserialize_array`` raises for the lowest failing record."""
+    from . import cabi
+    if cabi.check_where(where) is None:
+        raise TypeError("argument 'where': expected a term (name, op, value) or a list of terms")
+    _get_schema(schema)
+    cabi.Filter.get(schema, where)
+    data, offs = _pack_records(list)
+    return cabi.filter_packed(data, offs, schema, where, devices=_current_devices())
 
 
 def _decode_tolerant(records, schema, num_chunks, columns, max_errors, reader_schema=None):
@@ -373,14 +410,16 @@ def device_count() -> int:
 
 
 def deserialize_to_device(records, schema, num_chunks, device: int = -1, stream: int = 0, *, columns=None, on_error="raise",
-                          max_errors=1024, reader_schema=None):
+                          max_errors=1024, reader_schema=None, where=None):
     """Extension: the same decode with the Arrow buffers left in HBM, every buffer a DLPack producer
     (``torch.from_dlpack(dec.batches[0].column("created_at").values)`` is an int64 tensor over the engine's memory, no copy).
     ``on_error="placeholder"``: the tolerant form -- the result's ``.errors`` lists the malformed records that were replaced by
-    ``placeholder_datum(schema)``; with ``"raise"`` (the default) ``.errors`` is ``[]``.  See ``pyruhvro_amd.device``."""
+    ``placeholder_datum(schema)``; with ``"raise"`` (the default) ``.errors`` is ``[]``.  ``where``: only the matching records
+    (see ``deserialize_array``; not with ``on_error="placeholder"``); the result's ``.kept`` says how many.  See
+    ``pyruhvro_amd.device``."""
     from .device import deserialize_to_device as f
     return f(records, schema, num_chunks, device=device, stream=stream, kernel=_kernel_mode, columns=columns, on_error=on_error,
-             max_errors=max_errors, reader_schema=reader_schema)
+             max_errors=max_errors, reader_schema=reader_schema, where=where)
 
 
 def kernels_ready(schema: str, encode: bool = False, timeout_ms: int = 0, *, columns=None, reader_schema=None) -> bool:
@@ -403,7 +442,7 @@ __all__ = [
     "serialize_record_batch_with_stats",
     "serialize_record_batch", "serialize_record_batch_spawn", "arrow_schema", "device_count", "set_kernel_mode",
     "deserialize_binary_array", "set_devices", "kernels_ready", "prebuild", "deserialize_to_device",
-    "placeholder_datum", "validate_records", "RecordError", "deserialize_array_tolerant", "deserialize_array_threaded_tolerant",
+    "placeholder_datum", "validate_records", "filter_records", "RecordError", "deserialize_array_tolerant", "deserialize_array_threaded_tolerant",
     "deserialize_binary_array_tolerant",
     "container_info", "read_container", "read_container_to_device", "write_container", "ContainerInfo",
     "read_container_tolerant", "read_container_to_device_tolerant", "BlockError",

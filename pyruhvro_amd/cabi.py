@@ -419,11 +419,13 @@ def shard_chunks(n: int, num_chunks: int, n_shards: int, shard: int):
 
 
 def decode_packed(data: np.ndarray, offsets: np.ndarray, schema_json: str, num_chunks: int,
-                  device: int = -1, want_stats: bool = False, kernel: int = KERNEL_AUTO, devices=None, *, columns=None, reader_schema=None):
+                  device: int = -1, want_stats: bool = False, kernel: int = KERNEL_AUTO, devices=None, *, columns=None, reader_schema=None,
+                  where=None):
     """rh_decode_packed: one contiguous payload + u64 offsets (host memory) -> list[RecordBatch].
     `devices`: shard the chunks over these HIP devices (rh_opts.devices); with want_stats the stats dict then carries
-    the per-shard stats under "device_stats"."""
+    the per-shard stats under "device_stats".  `where`: rh_decode_packed_where (a row filter, see check_where)."""
     L = lib()
+    flt = Filter.get(schema_json, where) if where is not None else None      # ValueError "where: ..." before any device work
     s = Schema.get(schema_json, columns, reader_schema)
     data = np.ascontiguousarray(data, dtype=np.uint8)
     offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
@@ -434,8 +436,12 @@ def decode_packed(data: np.ndarray, offsets: np.ndarray, schema_json: str, num_c
     st = RhStats()
     err = C.c_char_p()
     opts, keep = make_opts(device, kernel, None, devices)
-    rc = L.rh_decode_packed(s.handle, data.ctypes.data, offsets.ctypes.data, n, num_chunks, C.byref(opts), arr,
-                            C.byref(out_k), C.byref(st), C.byref(err))
+    if flt is not None:
+        rc = _filter_sym("rh_decode_packed_where")(s.handle, data.ctypes.data, offsets.ctypes.data, n, num_chunks, C.byref(opts), arr,
+                                                   C.byref(out_k), C.byref(st), C.byref(err), flt.handle, None)
+    else:
+        rc = L.rh_decode_packed(s.handle, data.ctypes.data, offsets.ctypes.data, n, num_chunks, C.byref(opts), arr,
+                                C.byref(out_k), C.byref(st), C.byref(err))
     if rc != RH_OK:
         _raise(rc, err)
     out = _import_chunks(arr, out_k.value, s.arrow_schema)
@@ -448,10 +454,12 @@ def decode_packed(data: np.ndarray, offsets: np.ndarray, schema_json: str, num_c
 
 
 def decode_slices(ptrs: np.ndarray, lens: np.ndarray, schema_json: str, num_chunks: int,
-                  device: int = -1, want_stats: bool = False, kernel: int = KERNEL_AUTO, devices=None, *, columns=None, reader_schema=None):
+                  device: int = -1, want_stats: bool = False, kernel: int = KERNEL_AUTO, devices=None, *, columns=None, reader_schema=None,
+                  where=None):
     """rh_decode: one (pointer, length) pair per record, the form the CPython boundary extracts from list[bytes]
-    (u64 addresses / u64 lengths; the caller keeps the pointed-to memory alive) -> list[RecordBatch]."""
+    (u64 addresses / u64 lengths; the caller keeps the pointed-to memory alive) -> list[RecordBatch].  `where`: rh_decode_where."""
     L = lib()
+    flt = Filter.get(schema_json, where) if where is not None else None
     s = Schema.get(schema_json, columns, reader_schema)
     ptrs = np.ascontiguousarray(ptrs, dtype=np.uint64)
     lens = np.ascontiguousarray(lens, dtype=np.uint64)
@@ -462,12 +470,161 @@ def decode_slices(ptrs: np.ndarray, lens: np.ndarray, schema_json: str, num_chun
     st = RhStats()
     err = C.c_char_p()
     opts, keep = make_opts(device, kernel, None, devices)
-    rc = L.rh_decode(s.handle, ptrs.ctypes.data, lens.ctypes.data, n, num_chunks, C.byref(opts), arr,
-                     C.byref(out_k), C.byref(st), C.byref(err))
+    if flt is not None:
+        rc = _filter_sym("rh_decode_where")(s.handle, ptrs.ctypes.data, lens.ctypes.data, n, num_chunks, C.byref(opts), arr,
+                                            C.byref(out_k), C.byref(st), C.byref(err), flt.handle, None)
+    else:
+        rc = L.rh_decode(s.handle, ptrs.ctypes.data, lens.ctypes.data, n, num_chunks, C.byref(opts), arr,
+                         C.byref(out_k), C.byref(st), C.byref(err))
     if rc != RH_OK:
         _raise(rc, err)
     out = _import_chunks(arr, out_k.value, s.arrow_schema)
     return (out, st.as_dict()) if want_stats else out
+
+
+# Row filters (include/ruhvro_hip.h): symbols added without a change of the ABI version, looked up by name.
+class RhFilterTerm(C.Structure):
+    _fields_ = [("name", C.c_char_p), ("op", C.c_char_p), ("value_kind", C.c_int32), ("reserved", C.c_int32), ("i", C.c_int64),
+                ("d", C.c_double), ("bytes", C.c_char_p), ("len", C.c_uint64)]
+
+
+FILTER_VALUE_NONE, FILTER_VALUE_INT, FILTER_VALUE_DOUBLE, FILTER_VALUE_BOOL, FILTER_VALUE_BYTES, FILTER_VALUE_BIGINT = range(6)
+FILTER_SYMBOLS = ("rh_filter_compile", "rh_filter_free", "rh_filter_packed", "rh_filter_device", "rh_decode_where",
+                  "rh_decode_packed_where", "rh_decode_device_where", "rh_filter_last")
+
+
+def _filter_sym(name: str):
+    f = getattr(lib(), name, None)          # (ctypes: dlsym)
+    if f is None:
+        raise RuntimeError(f"libruhvro_hip.so has no {name}: the library was built before row filters")
+    if f.argtypes is None:
+        L = lib()
+        f.restype, f.argtypes = {
+            "rh_filter_compile": (C.c_int, [C.c_void_p, C.POINTER(RhFilterTerm), C.c_uint32, C.POINTER(C.c_void_p), C.POINTER(C.c_char_p)]),
+            "rh_filter_free": (None, [C.c_void_p]),
+            "rh_filter_packed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(RhOpts), C.c_void_p,
+                                           C.POINTER(C.c_uint64), C.POINTER(C.c_char_p)]),
+            "rh_filter_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.POINTER(RhOpts), C.c_void_p,
+                                           C.POINTER(C.c_uint64), C.POINTER(C.c_char_p)]),
+            "rh_decode_where": (C.c_int, L.rh_decode.argtypes + [C.c_void_p, C.POINTER(C.c_uint64)]),
+            "rh_decode_packed_where": (C.c_int, L.rh_decode.argtypes + [C.c_void_p, C.POINTER(C.c_uint64)]),
+            "rh_decode_device_where": (C.c_int, L.rh_decode_device.argtypes + [C.c_void_p, C.POINTER(C.c_uint64)]),
+            "rh_filter_last": (None, [C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+        }[name]
+    return f
+
+
+def check_where(where):
+    """The `where=` argument of the strict decode entry points -> None (no filter) or a tuple of terms (name, op, value).
+    One term ``(name, op, value)`` / ``(name, "is_null")`` or a list / tuple of terms, ANDed.  TypeError for anything that is
+    not a tuple or a list; ValueError ("where: ...") for a term of another shape.  What the terms may say is decided by
+    rh_filter_compile, which knows the schema."""
+    if where is None:
+        return None
+    if not isinstance(where, (tuple, list)):
+        raise TypeError("argument 'where': expected a term (name, op, value) or a list of terms, or None")
+    terms = [where] if (len(where) in (2, 3) and isinstance(where[0], str)) else list(where)
+    out = []
+    for k, t in enumerate(terms):
+        if not isinstance(t, (tuple, list)) or len(t) not in (2, 3) or not isinstance(t[0], str) or not isinstance(t[1], str):
+            raise ValueError(f"where: term {k} ({t!r}) is not (name, op, value) or (name, 'is_null' / 'not_null')")
+        out.append((t[0], t[1], t[2] if len(t) == 3 else None))
+    return tuple(out)
+
+
+def _filter_term(name: str, op: str, value) -> RhFilterTerm:
+    t = RhFilterTerm()
+    t.name, t.op = name.encode(), op.encode()
+    if value is None:
+        t.value_kind = FILTER_VALUE_NONE
+    elif isinstance(value, (bool, np.bool_)):
+        t.value_kind, t.i = FILTER_VALUE_BOOL, int(bool(value))
+    elif isinstance(value, (int, np.integer)):
+        value = int(value)
+        try:
+            t.d = float(value)
+        except OverflowError:
+            t.d = float("inf") if value > 0 else float("-inf")
+        if -(1 << 63) <= value < (1 << 63):
+            t.value_kind, t.i = FILTER_VALUE_INT, value
+        else:
+            t.value_kind = FILTER_VALUE_BIGINT
+    elif isinstance(value, (float, np.floating)):
+        t.value_kind, t.d = FILTER_VALUE_DOUBLE, float(value)
+    elif isinstance(value, (str, bytes, bytearray)):
+        raw = value.encode("utf-8") if isinstance(value, str) else bytes(value)
+        t.value_kind, t.bytes, t.len = FILTER_VALUE_BYTES, raw, len(raw)
+    else:
+        raise ValueError(f"where: field '{name}': a value of type {type(value).__name__} cannot be compared with")
+    return t
+
+
+class Filter:
+    """Compiled predicate (rh_filter*) of one writer schema; cached by (schema, terms)."""
+
+    _cache: dict = {}
+
+    def __init__(self, schema_json: str, terms):
+        arr = (RhFilterTerm * max(len(terms), 1))(*[_filter_term(*t) for t in terms])
+        out, err = C.c_void_p(), C.c_char_p()
+        rc = _filter_sym("rh_filter_compile")(Schema.get(schema_json).handle, arr, len(terms), C.byref(out), C.byref(err))
+        if rc != RH_OK:
+            _raise(rc, err)
+        self.handle = out.value
+
+    @classmethod
+    def get(cls, schema_json: str, where) -> "Filter":
+        terms = check_where(where)
+        if terms is None:
+            raise ValueError("where: no predicate")
+        key = (schema_json, tuple((n, o, type(v).__name__, repr(v)) for n, o, v in terms))
+        f = cls._cache.get(key)
+        if f is None:
+            f = cls._cache[key] = cls(schema_json, terms)
+        return f
+
+
+def _keep_mask(words: np.ndarray, n: int) -> np.ndarray:
+    return np.unpackbits(words.view(np.uint8), bitorder="little")[:n].astype(bool)
+
+
+def filter_packed(data: np.ndarray, offsets: np.ndarray, schema_json: str, where, device: int = -1, devices=None) -> np.ndarray:
+    """rh_filter_packed: the filter kernel alone -> numpy bool[n], True where the record is kept.  A malformed record raises
+    the strict decode's message for the lowest failing record."""
+    flt = Filter.get(schema_json, where)
+    data = np.ascontiguousarray(data, dtype=np.uint8)
+    offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+    n = len(offsets) - 1
+    words = np.zeros(max((n + 63) // 64, 1), dtype=np.uint64)
+    kept, err = C.c_uint64(), C.c_char_p()
+    opts, _keep = make_opts(device, 0, None, devices)
+    rc = _filter_sym("rh_filter_packed")(flt.handle, data.ctypes.data, offsets.ctypes.data, n, C.byref(opts), words.ctypes.data,
+                                         C.byref(kept), C.byref(err))
+    if rc != RH_OK:
+        _raise(rc, err)
+    mask = _keep_mask(words, n)
+    assert int(mask.sum()) == kept.value
+    return mask
+
+
+def filter_device(d_data: int, d_offsets: int, data_len: int, n: int, schema_json: str, where, device: int = -1, stream: int = 0) -> np.ndarray:
+    """rh_filter_device on raw device pointers -> numpy bool[n] (host memory)."""
+    flt = Filter.get(schema_json, where)
+    words = np.zeros(max((n + 63) // 64, 1), dtype=np.uint64)
+    kept, err = C.c_uint64(), C.c_char_p()
+    opts, _keep = make_opts(device, 0, stream, None)
+    rc = _filter_sym("rh_filter_device")(flt.handle, d_data, d_offsets, data_len, n, C.byref(opts), words.ctypes.data, C.byref(kept),
+                                         C.byref(err))
+    if rc != RH_OK:
+        _raise(rc, err)
+    return _keep_mask(words, n)
+
+
+def filter_last() -> dict:
+    """rh_filter_last: the most recent filtered call of this process."""
+    f_ms, g_ms, n, kept = C.c_float(), C.c_float(), C.c_uint64(), C.c_uint64()
+    _filter_sym("rh_filter_last")(C.byref(f_ms), C.byref(g_ms), C.byref(n), C.byref(kept))
+    return {"filter_ms": f_ms.value, "gather_ms": g_ms.value, "n": int(n.value), "kept": int(kept.value)}
 
 
 # One malformed record of a tolerant / validation call: its index in the call's input and the message the strict call raises
@@ -696,23 +853,31 @@ def encode_device(batch_array_addr: int, batch_schema_addr: int, schema_json: st
 def decode_device(d_data: int, d_offsets: int, data_len: int, n: int, schema_json: str, num_chunks: int,
                   device: int = -1, stream: int = 0, want_stats: bool = True, kernel: int = KERNEL_AUTO,
                   chunk_rows: int = 0, asynchronous: bool = False, two_pass: bool = False, single_pass: bool = False,
-                  *, columns=None, reader_schema=None) -> DeviceResult:
+                  *, columns=None, reader_schema=None, where=None) -> DeviceResult:
     """rh_decode_device on raw device pointers (e.g. torch tensors' data_ptr()).  chunk_rows: explicit geometry
     for a range of a larger call's chunks (rh_opts.chunk_rows).  asynchronous: RH_ASYNC -- the result is returned
-    unsettled (DeviceResult.wait() settles it and fills .stats; every accessor settles implicitly)."""
+    unsettled (DeviceResult.wait() settles it and fills .stats; every accessor settles implicitly).  `where`:
+    rh_decode_device_where (a row filter, see check_where); the result's `.kept` is the number of records it kept."""
     L = lib()
+    flt = Filter.get(schema_json, where) if where is not None else None
     s = Schema.get(schema_json, columns, reader_schema)
     out = C.c_void_p()
     st = RhStats()
     err = C.c_char_p()
     opts, _keep = make_opts(device, kernel | (RH_ASYNC if asynchronous else 0) | (RH_TWO_PASS if two_pass else 0) |
                             (RH_SINGLE_PASS if single_pass else 0), stream, None, chunk_rows)
-    rc = L.rh_decode_device(s.handle, d_data, d_offsets, data_len, n, num_chunks, C.byref(opts), C.byref(out),
-                            C.byref(st) if want_stats else None, C.byref(err))
+    kept = C.c_uint64(n)
+    if flt is not None:
+        rc = _filter_sym("rh_decode_device_where")(s.handle, d_data, d_offsets, data_len, n, num_chunks, C.byref(opts), C.byref(out),
+                                                   C.byref(st) if want_stats else None, C.byref(err), flt.handle, C.byref(kept))
+    else:
+        rc = L.rh_decode_device(s.handle, d_data, d_offsets, data_len, n, num_chunks, C.byref(opts), C.byref(out),
+                                C.byref(st) if want_stats else None, C.byref(err))
     if rc != RH_OK:
         _raise(rc, err)
     r = DeviceResult(out.value, s, st.as_dict())
     r._want_stats = want_stats
+    r.kept = int(kept.value)
     return r
 
 

@@ -246,6 +246,7 @@ class DeviceDecode:
         self.schema = schema
         self.stats = result.stats
         self.errors = list(result.errors)      # on_error="placeholder": the malformed records that were replaced
+        self.kept = getattr(result, "kept", None)      # where=: the records the filter kept (else the records of the call)
         self.device = 0
         self.batches: List[DeviceBatch] = []
         L = cabi.lib()
@@ -306,7 +307,7 @@ def _pack(records) -> tuple:
 
 
 def deserialize_to_device(records, schema: str, num_chunks: int, device: int = -1, stream: int = 0, kernel: int = 0, *, columns=None,
-                          on_error: str = "raise", max_errors: int = 1024, reader_schema=None) -> DeviceDecode:
+                          on_error: str = "raise", max_errors: int = 1024, reader_schema=None, where=None) -> DeviceDecode:
     """Extension.  Decode like ``deserialize_array_threaded(records, schema, num_chunks)`` but leave the Arrow
     buffers in HBM.  ``records``: a list of ``bytes``, a pyarrow ``BinaryArray`` / ``LargeBinaryArray`` (packed on the host and
     uploaded once), or a pair ``(data, offsets)`` of device arrays that already hold the packed payload and its n + 1 uint64
@@ -318,9 +319,14 @@ def deserialize_to_device(records, schema: str, num_chunks: int, device: int = -
     Errors are the reference's: ``ValueError`` with its message for a malformed datum or an unsupported schema.
     ``on_error="placeholder"``: a malformed record does not abort the call; it is replaced by ``placeholder_datum(schema)`` and
     listed in the result's ``.errors`` (``[RecordError(index, message)]``, ascending; at most ``max_errors``, beyond which the
-    call raises as with ``"raise"``)."""
+    call raises as with ``"raise"``).
+    ``where``: decode only the records that match this predicate (``deserialize_array``); the compacted record list lives in a
+    device buffer the result owns, ``.kept`` is the number of records kept.  Not with ``on_error="placeholder"``."""
     if on_error not in ("raise", "placeholder"):
         raise ValueError("on_error: expected 'raise' or 'placeholder'")
+    cabi.check_where(where)
+    if where is not None and on_error == "placeholder":
+        raise ValueError("where: a tolerant decode does not take where= (tolerant filtering is a follow-up)")
     if not isinstance(num_chunks, int) or isinstance(num_chunks, bool):
         raise TypeError("argument 'num_chunks': expected int")
     if num_chunks < 0:
@@ -354,7 +360,7 @@ def deserialize_to_device(records, schema: str, num_chunks: int, device: int = -
                                             columns=columns, max_errors=check_max_errors(max_errors))
         else:
             r = cabi.decode_device(p_data, p_off, data_len, n, schema, num_chunks, device=device, stream=stream, kernel=kernel, columns=columns,
-                                   reader_schema=reader_schema)
+                                   reader_schema=reader_schema, where=where)
     finally:
         for k in keep:
             if isinstance(k, _DevMem):
