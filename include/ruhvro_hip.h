@@ -627,6 +627,45 @@ int rh_decode_device_where(const rh_schema* s, const void* d_data, const void* d
                            const rh_filter* filter, uint64_t* kept);
 void rh_filter_last(float* filter_ms, float* gather_ms, uint64_t* n, uint64_t* kept);
 
+/* Framed messages.  Added WITHOUT a change of RH_ABI_VERSION (7), discovered by symbol.
+ *
+ * Messages as a Kafka consumer holds them -- a header in front of every datum -- are checked, partitioned by writer schema id and
+ * stripped of their headers on the device; each class is then decoded by the unchanged strict decode with its own schema.
+ *   RH_FRAMING_CONFLUENT      00 | schema id, 4 bytes big-endian | datum                       (ids 0 .. 2^32 - 1)
+ *   RH_FRAMING_SINGLE_OBJECT  C3 01 | CRC-64-AVRO fingerprint, 8 bytes little-endian | datum  (ids 0 .. 2^64 - 1)
+ * rh_frame_split_packed / rh_frame_split_device: `ids` are the m (1 .. 32) wire ids of the call, ascending and distinct; class c is
+ * the messages whose header carries ids[c], in input order.  Framing is judged over the whole list before anything else happens:
+ * the message of the lowest index that is shorter than the header, does not start with the marker, or -- without
+ * RH_FRAME_SKIP_UNKNOWN -- carries an id that is not in `ids` fails the call with RH_ERR_DECODE and a message that starts with
+ * "framed: message <i> ".  With RH_FRAME_SKIP_UNKNOWN the messages of unknown ids form class m: they have indices and no payload.
+ * RH_FRAME_CLASSIFY_ONLY (implies the former): the verdicts alone, no partition.  The host form uploads the list in one piece (not
+ * the pinned, pipelined path of rh_decode); the device form takes rh_decode_device's input (payload 16-byte aligned).  One device:
+ * rh_opts.devices and RH_ASYNC are refused with RH_ERR_ARGUMENT.  The split owns device memory until rh_frame_split_free.
+ * rh_frame_split_count: messages of class c (c = m: the unknown ids).  rh_frame_split_classes: one byte per message -- its class,
+ * or 0xFD for an unknown id -- into n bytes of host memory.  rh_frame_split_indices: class c's ascending positions in the input,
+ * into rh_frame_split_count(c) int64 of host memory.
+ * rh_frame_decode_class: rh_decode_packed of class c's payloads with `s` -- plain, projected or resolved, made from that class's
+ * writer schema; num_chunks applies to the class (out_chunks: room for rh_clamp_chunks(rh_frame_split_count(c), num_chunks)).  A
+ * malformed payload raises "framed: schema id <id>: " and the strict decode's message for the class's list.  The result takes the
+ * class's payloads over: a class decodes once.
+ * rh_frame_last: GPU time of the most recent split's classify kernel, of its scan and offsets kernels, and of its gather. */
+typedef struct rh_frame_split rh_frame_split;
+#define RH_FRAMING_CONFLUENT 0
+#define RH_FRAMING_SINGLE_OBJECT 1
+#define RH_FRAME_SKIP_UNKNOWN 1
+#define RH_FRAME_CLASSIFY_ONLY 2
+int rh_frame_split_packed(const uint8_t* data, const uint64_t* offsets, uint64_t n, const uint64_t* ids, uint32_t m, uint32_t framing,
+                          uint32_t flags, const rh_opts* opts, rh_frame_split** out, char** err);
+int rh_frame_split_device(const void* d_data, const void* d_offsets, uint64_t data_len, uint64_t n, const uint64_t* ids, uint32_t m,
+                          uint32_t framing, uint32_t flags, const rh_opts* opts, rh_frame_split** out, char** err);
+uint64_t rh_frame_split_count(const rh_frame_split* split, uint32_t c);
+int rh_frame_split_classes(const rh_frame_split* split, uint8_t* out, char** err);
+int rh_frame_split_indices(const rh_frame_split* split, uint32_t c, int64_t* out, char** err);
+int rh_frame_decode_class(rh_frame_split* split, uint32_t c, const rh_schema* s, uint64_t num_chunks, const rh_opts* opts,
+                          struct ArrowArray* out_chunks, uint32_t* out_k, rh_stats* stats, char** err);
+void rh_frame_split_free(rh_frame_split* split);
+void rh_frame_last(float* classify_ms, float* scan_offsets_ms, float* gather_ms, uint64_t* n);
+
 /* Measurement hook, not part of the drop-in surface: the host-side gather of a `shards`-GPU rh_decode call (every shard's
  * record slices copied into its staging buffer by its own host thread + `threads_per_shard` helpers, all shards at once)
  * without the GPUs -- pageable destinations (pinned = 0, runs on a box with no device), pinned ones (1), or pageable ones placed

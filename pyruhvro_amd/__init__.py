@@ -446,10 +446,12 @@ __all__ = [
     "deserialize_binary_array_tolerant",
     "container_info", "read_container", "read_container_to_device", "write_container", "ContainerInfo",
     "read_container_tolerant", "read_container_to_device_tolerant", "BlockError",
+    "deserialize_framed", "frame_split", "schema_fingerprint", "FramedGroup", "FramedResult",
 ]
 
 from .container import ContainerInfo, container_info, read_container, read_container_to_device, write_container  # noqa: E402
 from .container import BlockError, read_container_tolerant, read_container_to_device_tolerant  # noqa: E402
+from .framing import FramedGroup, FramedResult, deserialize_framed, frame_split, schema_fingerprint  # noqa: E402
 
 
 def __getattr__(name):      # (RecordError lives beside the ctypes wrappers that build it; cabi needs numpy, imported on first use)

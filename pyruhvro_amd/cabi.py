@@ -627,6 +627,124 @@ def filter_last() -> dict:
     return {"filter_ms": f_ms.value, "gather_ms": g_ms.value, "n": int(n.value), "kept": int(kept.value)}
 
 
+# Framed messages (include/ruhvro_hip.h): symbols added without a change of the ABI version, looked up by name.
+FRAMINGS = {"confluent": 0, "single_object": 1}
+FRAME_SKIP_UNKNOWN, FRAME_CLASSIFY_ONLY = 1, 2
+FRAME_UNKNOWN = 0xFD      # the verdict byte of a well-framed message whose id is not in the call's list
+FRAME_SYMBOLS = ("rh_frame_split_packed", "rh_frame_split_device", "rh_frame_split_count", "rh_frame_split_classes",
+                 "rh_frame_split_indices", "rh_frame_decode_class", "rh_frame_split_free", "rh_frame_last")
+
+
+def _frame_sym(name: str):
+    f = getattr(lib(), name, None)
+    if f is None:
+        raise RuntimeError(f"libruhvro_hip.so has no {name}: the library was built before framed messages")
+    if f.argtypes is None:
+        tail = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(RhOpts), C.POINTER(C.c_void_p), C.POINTER(C.c_char_p)]
+        f.restype, f.argtypes = {
+            "rh_frame_split_packed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64] + tail),
+            "rh_frame_split_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64] + tail),
+            "rh_frame_split_count": (C.c_uint64, [C.c_void_p, C.c_uint32]),
+            "rh_frame_split_classes": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_char_p)]),
+            "rh_frame_split_indices": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(C.c_char_p)]),
+            "rh_frame_decode_class": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.POINTER(RhOpts), C.POINTER(ArrowArray),
+                                                C.POINTER(C.c_uint32), C.POINTER(RhStats), C.POINTER(C.c_char_p)]),
+            "rh_frame_split_free": (None, [C.c_void_p]),
+            "rh_frame_last": (None, [C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_uint64)]),
+        }[name]
+    return f
+
+
+class FrameSplit:
+    """rh_frame_split*: framed messages checked, partitioned by wire id and stripped of their headers on the device.  `ids`: the
+    call's wire ids, ascending and distinct (unsigned).  Class c is the messages that carry ids[c]; class len(ids) the messages
+    of unknown ids (only with FRAME_SKIP_UNKNOWN; indices, no payload)."""
+
+    def __init__(self, handle, n: int, ids, flags: int):
+        self.handle, self.n, self.ids, self.flags = handle, n, tuple(ids), flags
+
+    @classmethod
+    def _make(cls, sym: str, lead, n: int, ids, framing: int, flags: int, device: int, kernel: int, devices, stream=None):
+        arr = np.ascontiguousarray(ids, dtype=np.uint64)
+        out, err = C.c_void_p(), C.c_char_p()
+        opts, _keep = make_opts(device, kernel, stream, devices)
+        rc = _frame_sym(sym)(*lead, n, arr.ctypes.data, len(arr), framing, flags, C.byref(opts), C.byref(out), C.byref(err))
+        if rc != RH_OK:
+            _raise(rc, err)
+        return cls(out.value, n, [int(x) for x in arr], flags)
+
+    @classmethod
+    def packed(cls, data: np.ndarray, offsets: np.ndarray, ids, framing: int, flags: int = 0, device: int = -1, kernel: int = 0,
+               devices=None) -> "FrameSplit":
+        """rh_frame_split_packed: one contiguous payload + u64 offsets (host memory)."""
+        data = np.ascontiguousarray(data, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        return cls._make("rh_frame_split_packed", (data.ctypes.data, offsets.ctypes.data), len(offsets) - 1, ids, framing, flags, device,
+                         kernel, devices)
+
+    @classmethod
+    def device(cls, d_data: int, d_offsets: int, data_len: int, n: int, ids, framing: int, flags: int = 0, device: int = -1,
+               stream: int = 0) -> "FrameSplit":
+        """rh_frame_split_device on raw device pointers (rh_decode_device's input)."""
+        return cls._make("rh_frame_split_device", (d_data, d_offsets, data_len), n, ids, framing, flags, device, 0, None, stream)
+
+    def count(self, c: int) -> int:
+        return int(_frame_sym("rh_frame_split_count")(self.handle, c))
+
+    def classes(self) -> np.ndarray:
+        """numpy int16[n]: the class of every message, -1 for an unknown id."""
+        raw = np.zeros(max(self.n, 1), dtype=np.uint8)
+        err = C.c_char_p()
+        rc = _frame_sym("rh_frame_split_classes")(self.handle, raw.ctypes.data, C.byref(err))
+        if rc != RH_OK:
+            _raise(rc, err)
+        out = raw[:self.n].astype(np.int16)
+        out[raw[:self.n] == FRAME_UNKNOWN] = -1
+        return out
+
+    def indices(self, c: int) -> np.ndarray:
+        """numpy int64[count(c)]: class c's ascending positions in the input."""
+        out = np.zeros(self.count(c), dtype=np.int64)
+        err = C.c_char_p()
+        rc = _frame_sym("rh_frame_split_indices")(self.handle, c, out.ctypes.data, C.byref(err))
+        if rc != RH_OK:
+            _raise(rc, err)
+        return out
+
+    def decode(self, c: int, schema_json: str, num_chunks: int, device: int = -1, kernel: int = KERNEL_AUTO, want_stats: bool = False, *,
+               columns=None, reader_schema=None):
+        """rh_frame_decode_class: the strict decode of class c's payloads with its schema -> list[RecordBatch].  Once per class."""
+        s = Schema.get(schema_json, columns, reader_schema)
+        k = lib().rh_clamp_chunks(self.count(c), num_chunks)
+        arr = (ArrowArray * k)()
+        out_k, st, err = C.c_uint32(), RhStats(), C.c_char_p()
+        opts, _keep = make_opts(device, kernel, None, None)
+        rc = _frame_sym("rh_frame_decode_class")(self.handle, c, s.handle, num_chunks, C.byref(opts), arr, C.byref(out_k), C.byref(st),
+                                                 C.byref(err))
+        if rc != RH_OK:
+            _raise(rc, err)
+        out = _import_chunks(arr, out_k.value, s.arrow_schema)
+        return (out, st.as_dict()) if want_stats else out
+
+    def free(self):
+        if self.handle:
+            _frame_sym("rh_frame_split_free")(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+def frame_last() -> dict:
+    """rh_frame_last: GPU time of the most recent split of this process, kernel by kernel."""
+    c_ms, s_ms, g_ms, n = C.c_float(), C.c_float(), C.c_float(), C.c_uint64()
+    _frame_sym("rh_frame_last")(C.byref(c_ms), C.byref(s_ms), C.byref(g_ms), C.byref(n))
+    return {"classify_ms": c_ms.value, "scan_offsets_ms": s_ms.value, "gather_ms": g_ms.value, "n": int(n.value)}
+
+
 # One malformed record of a tolerant / validation call: its index in the call's input and the message the strict call raises
 # when that record is the lowest failing one.
 RecordError = namedtuple("RecordError", ["index", "message"])

@@ -305,12 +305,8 @@ static rh_device_result* decode_device_where(rh_schema* s, rh_filter* f, const u
   return r;
 }
 
-// host records -> one plain upload (not the pinned, pipelined list path of rh_decode)
-struct Uploaded {
-  Lease data, off;
-  uint64_t bytes = 0;
-};
-static void upload(const Source& src, uint64_t n, int device, hipStream_t stream, Uploaded& u) {
+// host records -> one plain upload (not the pinned, pipelined list path of rh_decode); also the framed calls' (engine_frame.cpp)
+void upload(const Source& src, uint64_t n, int device, hipStream_t stream, Uploaded& u) {
   std::vector<uint64_t> hoff(n + 1);
   std::vector<uint8_t> hdata;
   const uint8_t* hsrc = nullptr;

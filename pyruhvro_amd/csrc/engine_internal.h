@@ -748,4 +748,12 @@ int decode_host_impl(rh_schema* s, const Source& src, uint64_t n, uint64_t num_c
                      ArrowArray* out_chunks, uint32_t* out_k, rh_stats* stats);
 uint64_t gather_into(const uint8_t* const* ptrs, const uint64_t* lens, uint64_t n, unsigned nt_in, uint8_t* hdst, uint64_t* hoff);
 
+// Host records -> device memory in one plain upload (engine_filter.cpp): the payload 16-byte aligned with 64 zero bytes behind it,
+// n + 1 offsets that start at 0.  What the filtered and the framed host calls read; not the pinned, pipelined list path.
+struct Uploaded {
+  Lease data, off;
+  uint64_t bytes = 0;
+};
+void upload(const Source& src, uint64_t n, int device, hipStream_t stream, Uploaded& u);
+
 }  // namespace rhe
