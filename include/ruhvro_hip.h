@@ -627,6 +627,40 @@ int rh_decode_device_where(const rh_schema* s, const void* d_data, const void* d
                            const rh_filter* filter, uint64_t* kept);
 void rh_filter_last(float* filter_ms, float* gather_ms, uint64_t* n, uint64_t* kept);
 
+/* Row filters in the container read.  Added WITHOUT a change of RH_ABI_VERSION (7), discovered by symbol.
+ *
+ * rh_decode_blocks_where / rh_decode_blocks_device_where / rh_decode_cblocks_where / rh_decode_cblocks_device_where: their strict
+ * twins with a predicate of rh_filter_compile.  The split kernel's walk -- the one careful walk of every record a container read
+ * makes anyway -- also evaluates the predicate; the batches are those of rh_decode over the records it keeps, in file order
+ * (num_chunks applies to them; nothing kept gives what a decode of no records gives).  A call that keeps every record decodes
+ * the uploaded buffer where it is; otherwise the kept records are gathered into a device buffer the result owns.  `s` is plain,
+ * projected or resolved, made from the writer text the filter was compiled against (else RH_ERR_ARGUMENT).  They refuse what the
+ * blocks calls refuse (devices, RH_ASYNC, chunk_rows, the table, a block's size and count), with the same messages, and a
+ * malformed record or block fails the call exactly as it fails the strict twin, whether or not the record would have matched.
+ * rh_filter_blocks / rh_filter_cblocks: the split and the predicate alone -- bit i of keep_words[i / 64] (host memory, room for
+ * ceil(first[nb] / 64) words) says whether record i of the file is kept, *kept how many are.
+ * rh_container_where_last: GPU time of the most recent such call's split kernel and of its compaction (offsets + gather; 0 = none
+ * ran: every record was kept, or the call was rh_filter_*blocks), the records of the file and the records kept. */
+int rh_decode_blocks_where(const rh_schema* s, const uint8_t* data, uint64_t len, const uint64_t* start, const uint64_t* end,
+                           const uint64_t* first, uint64_t nb, uint64_t num_chunks, const rh_opts* opts, struct ArrowArray* out_chunks,
+                           uint32_t* out_k, rh_stats* stats, char** err, const rh_filter* filter, uint64_t* kept);
+int rh_decode_blocks_device_where(const rh_schema* s, const uint8_t* data, uint64_t len, const uint64_t* start, const uint64_t* end,
+                                  const uint64_t* first, uint64_t nb, uint64_t num_chunks, const rh_opts* opts, rh_device_result** out,
+                                  rh_stats* stats, char** err, const rh_filter* filter, uint64_t* kept);
+int rh_decode_cblocks_where(const rh_schema* s, const uint8_t* data, uint64_t len, const uint64_t* start, const uint64_t* end,
+                            const uint64_t* first, uint64_t nb, int codec, uint64_t max_block_bytes, uint64_t num_chunks, const rh_opts* opts,
+                            struct ArrowArray* out_chunks, uint32_t* out_k, rh_stats* stats, char** err, const rh_filter* filter,
+                            uint64_t* kept);
+int rh_decode_cblocks_device_where(const rh_schema* s, const uint8_t* data, uint64_t len, const uint64_t* start, const uint64_t* end,
+                                   const uint64_t* first, uint64_t nb, int codec, uint64_t max_block_bytes, uint64_t num_chunks,
+                                   const rh_opts* opts, rh_device_result** out, rh_stats* stats, char** err, const rh_filter* filter,
+                                   uint64_t* kept);
+int rh_filter_blocks(const rh_filter* f, const uint8_t* data, uint64_t len, const uint64_t* start, const uint64_t* end, const uint64_t* first,
+                     uint64_t nb, const rh_opts* opts, uint64_t* keep_words, uint64_t* kept, char** err);
+int rh_filter_cblocks(const rh_filter* f, const uint8_t* data, uint64_t len, const uint64_t* start, const uint64_t* end, const uint64_t* first,
+                      uint64_t nb, int codec, uint64_t max_block_bytes, const rh_opts* opts, uint64_t* keep_words, uint64_t* kept, char** err);
+void rh_container_where_last(float* split_ms, float* gather_ms, uint64_t* n, uint64_t* kept);
+
 /* Framed messages.  Added WITHOUT a change of RH_ABI_VERSION (7), discovered by symbol.
  *
  * Messages as a Kafka consumer holds them -- a header in front of every datum -- are checked, partitioned by writer schema id and

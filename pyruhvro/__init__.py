@@ -6,7 +6,8 @@ writer-encoded records into an evolved schema) and ``where=`` (decode only the r
 ``filter_records`` is that filter alone).  Beside them the tolerant decode: the
 ``*_tolerant`` functions replace malformed records by ``placeholder_datum(schema)`` and report all of them; and the Avro
 object container files: ``container_info`` / ``read_container`` / ``read_container_to_device`` / ``write_container``, and
-``read_container_tolerant`` / ``read_container_to_device_tolerant``, which salvage what a damaged file still holds; and framed
+``read_container_tolerant`` / ``read_container_to_device_tolerant``, which salvage what a damaged file still holds, and ``read_container_where`` / ``read_container_where_to_device`` /
+``filter_container``, which evaluate a ``where`` predicate in the walk that finds the file's records; and framed
 messages as a Kafka consumer holds them (Confluent wire format, Avro single-object encoding): ``deserialize_framed`` splits them
 by writer schema id on the GPU and decodes every group, ``frame_split`` is that split alone, ``schema_fingerprint`` the id a
 single-object header carries."""
@@ -22,6 +23,9 @@ from pyruhvro_amd import (  # noqa: F401
     read_container_tolerant,
     read_container_to_device_tolerant,
     BlockError,
+    read_container_where,
+    read_container_where_to_device,
+    filter_container,
     write_container,
     deserialize_array_tolerant,
     deserialize_array_threaded_tolerant,
@@ -43,6 +47,6 @@ __all__ = [
     "serialize_record_batch_spawn", "deserialize_to_device", "placeholder_datum", "validate_records", "filter_records", "RecordError",
     "deserialize_array_tolerant", "deserialize_array_threaded_tolerant", "deserialize_binary_array_tolerant",
     "container_info", "read_container", "read_container_to_device", "write_container", "read_container_tolerant",
-    "read_container_to_device_tolerant", "BlockError",
+    "read_container_to_device_tolerant", "BlockError", "read_container_where", "read_container_where_to_device", "filter_container",
     "deserialize_framed", "frame_split", "schema_fingerprint", "FramedGroup", "FramedResult",
 ]

@@ -1236,6 +1236,83 @@ def decode_cblocks_device(data, start, end, first, schema_json: str, num_chunks:
     return r
 
 
+# Row filters in the container read: the blocks calls with a predicate, looked up by symbol like the rest.
+CONTAINER_WHERE_SYMBOLS = ("rh_decode_blocks_where", "rh_decode_blocks_device_where", "rh_decode_cblocks_where", "rh_decode_cblocks_device_where",
+                           "rh_filter_blocks", "rh_filter_cblocks", "rh_container_where_last")
+_WHERE_TAIL = [C.c_void_p, C.POINTER(C.c_uint64)]
+
+
+def decode_blocks_where(data, start, end, first, schema_json: str, where, num_chunks: int, codec=None, max_block_bytes: int = 0,
+                        device: int = -1, want_stats: bool = False, kernel: int = KERNEL_AUTO, *, columns=None, reader_schema=None,
+                        to_device: bool = False, stream: int = 0):
+    """rh_decode_blocks_where / rh_decode_cblocks_where (codec given: start[b] .. end[b] are the payloads as they are in the file)
+    -> list[RecordBatch] of the records `where` keeps; to_device: the `_device` twins -> DeviceResult, its `.kept` the number of
+    records kept.  The predicate compiles first: ValueError "where: ..." before any device work."""
+    flt = Filter.get(schema_json, where)
+    s = Schema.get(schema_json, columns, reader_schema)
+    lead = _BLOCKS_LEAD if codec is None else _CBLOCKS_LEAD
+    name = ("rh_decode_blocks" if codec is None else "rh_decode_cblocks") + ("_device_where" if to_device else "_where")
+    if to_device:
+        fn = _container_sym(name, C.c_int, lead + [C.POINTER(C.c_void_p), C.POINTER(RhStats), C.POINTER(C.c_char_p)] + _WHERE_TAIL)
+    else:
+        fn = _container_sym(name, C.c_int, lead + [C.POINTER(ArrowArray), C.POINTER(C.c_uint32), C.POINTER(RhStats), C.POINTER(C.c_char_p)] +
+                            _WHERE_TAIL)
+    keep, nbytes, nb = _blocks_args(data, start, end, first)
+    head = [s.handle, keep[0].ctypes.data, nbytes, keep[1].ctypes.data, keep[2].ctypes.data, keep[3].ctypes.data, nb]
+    head += [num_chunks] if codec is None else [codec, max_block_bytes, num_chunks]
+    st, err, kept = RhStats(), C.c_char_p(), C.c_uint64()
+    opts, _keep = make_opts(device, kernel, stream if to_device else None)
+    if to_device:
+        out = C.c_void_p()
+        rc = fn(*head, C.byref(opts), C.byref(out), C.byref(st), C.byref(err), flt.handle, C.byref(kept))
+        if rc != RH_OK:
+            _raise(rc, err)
+        r = DeviceResult(out.value, s, st.as_dict())
+        r._want_stats = True
+        r.kept = int(kept.value)
+        return r
+    k = lib().rh_clamp_chunks(int(keep[3][-1]), num_chunks)
+    arr = (ArrowArray * k)()
+    out_k = C.c_uint32()
+    rc = fn(*head, C.byref(opts), arr, C.byref(out_k), C.byref(st), C.byref(err), flt.handle, C.byref(kept))
+    if rc != RH_OK:
+        _raise(rc, err)
+    out = _import_chunks(arr, out_k.value, s.arrow_schema)
+    return (out, st.as_dict()) if want_stats else out
+
+
+def filter_blocks(data, start, end, first, schema_json: str, where, codec=None, max_block_bytes: int = 0, device: int = -1) -> np.ndarray:
+    """rh_filter_blocks / rh_filter_cblocks: the split and the predicate alone -> numpy bool[n], True where the file's record is
+    kept.  A malformed record or block raises what the blocks call raises for it."""
+    flt = Filter.get(schema_json, where)
+    keep, nbytes, nb = _blocks_args(data, start, end, first)
+    n = int(keep[3][-1])
+    words = np.zeros(max((n + 63) // 64, 1), dtype=np.uint64)
+    kept, err = C.c_uint64(), C.c_char_p()
+    opts, _keep = make_opts(device, 0)
+    head = [flt.handle, keep[0].ctypes.data, nbytes, keep[1].ctypes.data, keep[2].ctypes.data, keep[3].ctypes.data, nb]
+    tail = [C.POINTER(RhOpts), C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_char_p)]
+    if codec is None:
+        fn = _container_sym("rh_filter_blocks", C.c_int, _BLOCKS_LEAD[:7] + tail)
+    else:
+        fn = _container_sym("rh_filter_cblocks", C.c_int, _BLOCKS_LEAD[:7] + [C.c_int, C.c_uint64] + tail)
+        head += [codec, max_block_bytes]
+    rc = fn(*head, C.byref(opts), words.ctypes.data, C.byref(kept), C.byref(err))
+    if rc != RH_OK:
+        _raise(rc, err)
+    mask = _keep_mask(words, n)
+    assert int(mask.sum()) == kept.value
+    return mask
+
+
+def container_where_last() -> dict:
+    """rh_container_where_last: the most recent filtered container read of this process."""
+    s_ms, g_ms, n, kept = C.c_float(), C.c_float(), C.c_uint64(), C.c_uint64()
+    _container_sym("rh_container_where_last", None, [C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)])(
+        C.byref(s_ms), C.byref(g_ms), C.byref(n), C.byref(kept))
+    return {"split_ms": s_ms.value, "gather_ms": g_ms.value, "n": int(n.value), "kept": int(kept.value)}
+
+
 def inflate_blocks(data, start, end, max_block_bytes: int = 0, device: int = -1):
     """rh_inflate_blocks: the raw-deflate streams at data[start[b] .. end[b]) inflated on the device -> (out, out_start, out_end,
     status): the accepted blocks back to back (bytes), where each lies (uint64 arrays; a failing block is empty), and one

@@ -4,6 +4,8 @@
     batches = pyruhvro.read_container("events.avro", 8)              # == deserialize_array_threaded(records_of(file), info.schema, 8)
     dec = pyruhvro.read_container_to_device(buf, 8)                  # as deserialize_to_device
     blob = pyruhvro.write_container(batch, schema, codec="deflate")  # bytes
+    batches = pyruhvro.read_container_where("events.avro", ("age", ">=", 30), 8)   # only the matching records
+    mask = pyruhvro.filter_container("events.avro", ("age", ">=", 30))             # numpy bool[num_records]
 
 A container block says "N records, M bytes" and nothing says where record j starts.  The file is uploaded as it is and a
 split kernel -- one lane per block -- walks the records with the writer's schema (the file's own, from its header) to find
@@ -182,6 +184,53 @@ def read_container_to_device(src, num_chunks=1, device: int = -1, *, columns=Non
         r = cabi.decode_blocks_device(buf, start, end, info._first, info.schema, num_chunks, device=device, kernel=P._kernel_mode,
                                       columns=columns, reader_schema=reader_schema)
     return DeviceDecode(r, cabi.Schema.get(info.schema, columns, reader_schema).arrow_schema)
+
+
+def _blocks_where(src, where, num_chunks, columns, reader_schema, inflate):
+    """`_blocks`, then the predicate compiled against the file's writer schema: TypeError for a `where` that is no tuple or list,
+    ValueError "where: ..." for what rh_filter_compile refuses -- behind the file's own errors, before any device work."""
+    from . import cabi
+    out = _blocks(src, num_chunks, columns, reader_schema, inflate)
+    if cabi.check_where(where) is None:
+        raise TypeError("argument 'where': expected a term (name, op, value) or a list of terms")
+    cabi.Filter.get(out[0].schema, where)
+    return out
+
+
+def read_container_where(src, where, num_chunks=1, *, columns=None, reader_schema=None, inflate=None):
+    """Extension.  ``read_container`` of the records that match a predicate: exactly ``deserialize_array_threaded([r for r in
+    records if keep(r)], info.schema, num_chunks, ...)`` over the file's records, in file order.  ``where`` is what
+    ``deserialize_array``'s ``where=`` takes -- a term ``(name, op, value)`` or a list of up to 8, ANDed -- and names top-level
+    fields of the file's writer schema, whether or not ``columns`` / ``reader_schema`` build them.  The records are chosen in
+    the walk that finds their offsets, before anything is decoded; the chunking applies to the kept records,
+    and nothing kept gives what a decode of the empty list gives.  A malformed record or block raises what ``read_container``
+    raises for the file, whether or not the record would have matched."""
+    import pyruhvro_amd as P
+    from . import cabi
+    info, buf, start, end, on_device = _blocks_where(src, where, num_chunks, columns, reader_schema, inflate)
+    return cabi.decode_blocks_where(buf, start, end, info._first, info.schema, where, num_chunks, cabi.CODEC_DEFLATE if on_device else None,
+                                    MAX_BLOCK_BYTES, kernel=P._kernel_mode, columns=columns, reader_schema=reader_schema)
+
+
+def read_container_where_to_device(src, where, num_chunks=1, device: int = -1, *, columns=None, reader_schema=None, inflate=None):
+    """Extension.  ``read_container_where`` with the Arrow buffers left in HBM: a ``DeviceDecode`` as ``read_container_to_device``
+    returns; its ``.kept`` is the number of records the predicate kept."""
+    import pyruhvro_amd as P
+    from . import cabi
+    from .device import DeviceDecode
+    info, buf, start, end, on_device = _blocks_where(src, where, num_chunks, columns, reader_schema, inflate)
+    r = cabi.decode_blocks_where(buf, start, end, info._first, info.schema, where, num_chunks, cabi.CODEC_DEFLATE if on_device else None,
+                                 MAX_BLOCK_BYTES, device=device, kernel=P._kernel_mode, columns=columns, reader_schema=reader_schema,
+                                 to_device=True)
+    return DeviceDecode(r, cabi.Schema.get(info.schema, columns, reader_schema).arrow_schema)
+
+
+def filter_container(src, where, *, inflate=None):
+    """Extension.  The row filter of ``read_container_where`` alone -- the split and the predicate, no decode: a numpy
+    ``bool[info.num_records]``, True where the file's record is kept (the twin of ``filter_records``)."""
+    from . import cabi
+    info, buf, start, end, on_device = _blocks_where(src, where, 1, None, None, inflate)
+    return cabi.filter_blocks(buf, start, end, info._first, info.schema, where, cabi.CODEC_DEFLATE if on_device else None, MAX_BLOCK_BYTES)
 
 
 BlockError = namedtuple("BlockError", ["block", "offset", "length", "kept", "lost", "message"])

@@ -2,6 +2,7 @@
 // host and device code.  Not one of the headers the specialised kernels include: the kernel-cache key does not see this file.
 #pragma once
 #include "program.h"
+#include "filter.h"      // FilterProgram, kFilterSlots: the predicate of rh_k_split_where
 
 namespace rh {
 
@@ -38,6 +39,17 @@ struct SParams {
   uint64_t* offsets;         // out [n + 1]: record i spans offsets[i] .. offsets[i + 1] (a block's last record runs on to the next block's first)
   SplitErr* err;             // out [nb]
   unsigned long long* first_bad;   // [0] ~(lowest failure key), 0 if none
+};
+
+// ---- row filters in the split walk (rh_decode_blocks_where, rh_filter_blocks) ---------------------------------
+// rh_k_split_where: rh_k_split whose walk also evaluates a predicate (filter_eval.h filter_walk) at the ops its terms mark.
+// S.prog is the program the predicate was compiled against (the filter's own plain compile of the writer's text).
+struct SWParams {
+  SParams S;
+  uint64_t* keep;               // [ceil(n / 64)] FParams::keep's format; ZERO at launch, filled by atomic ORs (container_where_core.h)
+  unsigned long long* kept;     // [kFilterSlots] kept records, summed by the host (zero at launch)
+  const uint8_t* cbytes;        // the byte comparands of the terms (FilterTerm::boff)
+  const FilterProgram* flt;     // the predicate, in DEVICE memory: its terms are read where a marked op is met (filter_eval.h f_eval)
 };
 
 // ---- tolerant container reads (rh_decode_blocks_tolerant) ----------------------------------------------------

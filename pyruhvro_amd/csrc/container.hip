@@ -6,6 +6,8 @@
 //                every op the way walk_drop.h runs the ops of a dropped field) once per record of its block, from global
 //                memory, and notes where every record began.  The program counter is wave-uniform; a lane whose block has
 //                fewer records than its neighbours' sits the other iterations out.
+//   rh_k_split_where   the same kernel with a predicate evaluated in the walk: a keep bit per record beside the
+//                offsets, for the filtered container reads (rh_decode_blocks_where, rh_filter_blocks).
 // The walk reads every byte once, one dependent stream per lane, and a wavefront takes as long as its fullest block: the
 // parallelism is the number of blocks ("What bounds it").
 #include <hip/hip_runtime.h>
@@ -18,6 +20,8 @@
 #include "walk.h"
 #include "walk_drop.h"
 #include "container.h"
+#include "filter_eval.h"             // filter_walk: the split walk that also evaluates a predicate (shared with filter.hip)
+#include "container_where_core.h"    // the keep-word accumulation of rh_k_split_where
 
 namespace rh {
 
@@ -131,6 +135,81 @@ extern "C" __global__ void __launch_bounds__(kBlock) rh_k_split(SParams S) { spl
 // rh_k_split_salvage: the same walk; a lane that fails stops ITS block and says how far it came.
 extern "C" __global__ void __launch_bounds__(kBlock) rh_k_split_salvage(SalvageParams P) { split_body<true>(P.S, P.rec); }
 
+// rh_k_split_where: rh_k_split -- the geometry, the block-based source, the offsets, the verdicts, all as
+// split_body<false> has them -- with filter_eval.h's filter_walk in place of split_walk: the one careful walk of every record
+// also says whether the record matches.  The lanes of a wavefront are at unrelated record indices, so there is no ballot: a lane
+// gathers the bits of one keep word in a register (container_where_core.h) and ORs it into W.keep -- zero at launch -- when it
+// moves on to the next word and when its block ends.  Nothing in this launch reads W.keep: the next launch does, so no fence.
+// A lane that sits an iteration out (go == false) runs the walk with L.live = false and f_eval's reads at its resting cursor:
+// at <= end <= S.data_len - base, and GlobalSrc bounds every read by that; its verdict is dropped (`go && ...`).  A lane that
+// fails stops its block: the records behind the malformed one have no bit and no offset, and the call fails on the host.
+extern "C" __global__ void __launch_bounds__(kBlock) rh_k_split_where(SWParams W) {
+  extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+  __shared__ unsigned long long wg_kept;
+  const SParams& S = W.S;
+  const uint32_t tid = threadIdx.x, lane = tid & 63;
+  const uint32_t depth = (uint32_t)(S.list_depth > 0 ? S.list_depth : 1);
+  uint32_t* const rem = reinterpret_cast<uint32_t*>(smem);
+  for (uint32_t d = 0; d < depth; d++) rem[d * kBlock + tid] = 0;
+  if (tid == 0) wg_kept = 0;
+  __syncthreads();
+
+  const uint64_t b = (uint64_t)blockIdx.x * kBlock + tid;
+  const bool mine = b < (uint64_t)S.nb;
+  uint64_t st = 0, en = 0, f0 = 0, f1 = 0;
+  if (mine) { st = S.start[b]; en = S.end[b]; f0 = S.first[b]; f1 = S.first[b + 1]; }
+  const uint64_t cnt = f1 - f0;
+  const uint64_t base = st & ~15ull;      // (as rh_k_split: the source is based at the block, cursors stay 32-bit)
+  const GlobalSrc src{S.data + base, S.data_len - base};
+  const uint32_t cur0 = (uint32_t)(st - base), end = cur0 + (uint32_t)(en - st);
+
+  SCtx c;
+  c.rem = rem; c.sym_off = S.sym_off; c.sym_data = S.sym_data;
+  c.lrow = tid; c.tid = tid; c.lane = lane; c.wave_live = true;
+  Lane L;
+  L.cur = cur0; L.end = end; L.err = 0; L.edetail = 0;
+  uint32_t code = 0;
+  int64_t detail = 0;
+  unsigned long long key = 0;
+  uint64_t j = 0, nkept = 0;
+  KeepAcc acc;
+  keep_acc_init(acc, f0);
+  const FMarks marks = f_marks(*W.flt);
+  for (;;) {
+    const bool go = mine && code == 0 && j < cnt;
+    if (!__any(go)) break;      // (wave-uniform)
+    const uint32_t at = L.cur;
+    if (go) S.offsets[f0 + j] = st + (uint64_t)(at - cur0);
+    L.err = 0; L.edetail = 0;
+    L.live = go; L.pres = go; L.redo = false; L.la = 0;
+    L.pstk = 0; L.lstk = 0; L.sstk = 0;
+    const bool match = filter_walk(S.prog, W.flt, marks, W.cbytes, c, src, L, go);
+    if (go && L.err) { code = L.err; detail = L.edetail; key = split_key_record(f0 + j); }
+    if (go && code == 0) {      // (f0 + j < f1 <= n: the word is inside W.keep)
+      uint64_t fw = 0, fb = 0;
+      if (keep_acc_step(acc, f0 + j, match, &fw, &fb)) atomicOr(reinterpret_cast<unsigned long long*>(W.keep + fw), (unsigned long long)fb);
+      nkept += match ? 1u : 0u;
+    }
+    if (!go) L.cur = at;        // (a lane that sat the record out stays where it was)
+    j += go ? 1u : 0u;
+  }
+  if (mine && keep_acc_finish(acc)) atomicOr(reinterpret_cast<unsigned long long*>(W.keep + acc.word), (unsigned long long)acc.bits);
+  if (mine && code == 0 && L.cur != end) { code = E_BLOCK_END; detail = (int64_t)(L.cur - cur0); key = split_key_block(f1); }
+  if (mine && code != 0) {
+    SplitErr e; e.code = code; e.pad = 0; e.detail = detail;
+    S.err[b] = e;
+    atomicMax(S.first_bad, ~key);
+  }
+  if (mine && b + 1 == (uint64_t)S.nb) S.offsets[f1] = en;      // offsets[n]: the last record ends with the last block
+
+  // the kept count: per wavefront, per workgroup in LDS, one add into slot (workgroup & 63) as rh_k_filter
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) nkept += __shfl_down(nkept, d, 64);
+  if (lane == 0 && nkept) atomicAdd(&wg_kept, (unsigned long long)nkept);
+  __syncthreads();
+  if (tid == 0 && wg_kept) atomicAdd(W.kept + (blockIdx.x & (kFilterSlots - 1)), wg_kept);
+}
+
 // rh_k_salvage_gather: what the salvage keeps, made contiguous.  One wavefront per keeping block copies the block's kept run to
 // its 16-byte aligned place (aligned 16-byte stores, loads at whatever alignment the source has, the tail byte by byte), zeroes
 // the pad behind it and rebases the run's record offsets.  Every branch below is wave-uniform but the lane-strided loops and
@@ -175,6 +254,18 @@ extern "C" int rh_launch_split(const rh::SParams* S, void* stream) {
   if (e) return e;
   const uint32_t nblocks = (S->nb + rh::kBlock - 1) / rh::kBlock;
   hipLaunchKernelGGL(rh::rh_k_split, dim3(nblocks), dim3(rh::kBlock), lds, (hipStream_t)stream, *S);
+  return (int)hipGetLastError();
+}
+
+// W->keep and W->kept are zero in stream order in front of this (the caller's memset)
+extern "C" int rh_launch_split_where(const rh::SWParams* W, void* stream) {
+  (void)hipGetLastError();
+  if (W->S.nb == 0) return 0;
+  const uint32_t lds = rh_split_lds_bytes(W->S.list_depth);
+  int e = (int)hipFuncSetAttribute(reinterpret_cast<const void*>(rh::rh_k_split_where), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 64);
+  if (e) return e;
+  const uint32_t nblocks = (W->S.nb + rh::kBlock - 1) / rh::kBlock;
+  hipLaunchKernelGGL(rh::rh_k_split_where, dim3(nblocks), dim3(rh::kBlock), lds, (hipStream_t)stream, *W);
   return (int)hipGetLastError();
 }
 

@@ -12,6 +12,7 @@
 extern "C" {
 uint32_t rh_split_lds_bytes(int list_depth);
 int rh_launch_split(const rh::SParams* S, void* stream);
+int rh_launch_split_where(const rh::SWParams* W, void* stream);
 int rh_launch_split_salvage(const rh::SalvageParams* P, void* stream);
 int rh_launch_salvage_gather(const rh::SalvageGatherParams* G, void* stream);
 int rh_launch_inflate_size(const rh::InflateParams* P, void* stream);
@@ -31,6 +32,20 @@ struct rh_container_info {
 namespace rhe {
 
 static std::atomic<float> g_split_last_ms{0.0f};
+
+// The predicate of a filtered container read (rh_decode_*blocks*_where, rh_filter_*blocks).
+struct WhereCall {
+  rh_filter* f = nullptr;
+  bool mask_only = false;            // rh_filter_blocks / rh_filter_cblocks: the split and the predicate alone, no decode
+  uint64_t* keep_words = nullptr;    // ... their out: host room for ceil(n / 64) words
+  uint64_t kept = 0;                 // out
+};
+static std::mutex g_where_last_mu;
+static struct { float split_ms = 0, gather_ms = 0; uint64_t n = 0, kept = 0; } g_where_last;
+static void note_where(float split_ms, float gather_ms, uint64_t n, uint64_t kept) {
+  std::lock_guard<std::mutex> g(g_where_last_mu);
+  g_where_last.split_ms = split_ms; g_where_last.gather_ms = gather_ms; g_where_last.n = n; g_where_last.kept = kept;
+}
 static constexpr uint64_t kMaxEmptyRecords = 1ull << 24;
 
 // The split walks the WRITER's plain program.  A projection or a resolution keeps the writer's text (CompiledSchema::json)
@@ -106,34 +121,57 @@ struct BlockTable {
 
 // Both roads from "the table and the bytes are on the device" onward: the split launch, its verdict, the device-input decode,
 // and the result's ownership of the buffers.  d_data holds `len` bytes of uncompressed blocks at [start[b], end[b]) (+ slack).
+// W: the call's predicate.  The split launch is then rh_k_split_where -- the same walk, the same offsets and
+// verdicts, and a keep bit per record -- and what is decoded is what the predicate keeps: everything (the buffers as they are,
+// no compaction launch), or the compacted list (compact_kept, as a filtered list call's).  W->mask_only: the call ends behind
+// the split with the keep words on the host, and returns nullptr.
 static rh_device_result* split_and_decode(rh_schema* s, rh_schema* plain, Lease& d_data, uint64_t len, BlockTable& T, const uint64_t* start,
                                           const uint64_t* end, const uint64_t* first, uint64_t nb, uint64_t num_chunks, const rh_opts* opts,
-                                          rh_stats* stats, int device, hipStream_t stream, float up_ms) {
+                                          rh_stats* stats, int device, hipStream_t stream, float up_ms, WhereCall* W = nullptr) {
   Lease& d_off = T.d_off;
   Lease& d_tab = T.d_tab;
   const uint64_t o_end = T.o_end, o_first = T.o_first, o_err = T.o_err, o_bad = T.o_bad;
   const uint64_t n = first[nb];
   const uint64_t data_end = nb ? end[nb - 1] : 0;
   float split_ms = 0;
+  Lease d_keep;      // W: the keep words, the kept slots, the byte comparands
   if (nb) {
-    const DeviceProgram& dp = device_program(plain, device);
-    rh::SParams S;
-    std::memset(&S, 0, sizeof S);
+    // (W: the predicate's pcs point into the filter's own plain compile of the same writer text)
+    rh_schema* const walked = W ? W->f->plain : plain;
+    const DeviceProgram& dp = device_program(walked, device);
+    rh::SWParams SW;
+    std::memset(&SW, 0, sizeof SW);
+    rh::SParams& S = SW.S;
     S.data = d_data.ptr(); S.data_len = len;
     S.start = (const uint64_t*)d_tab.ptr(); S.end = (const uint64_t*)(d_tab.ptr() + o_end); S.first = (const uint64_t*)(d_tab.ptr() + o_first);
-    S.nb = (uint32_t)nb; S.list_depth = plain->cs->list_depth;
+    S.nb = (uint32_t)nb; S.list_depth = walked->cs->list_depth;
     S.prog = dp.prog; S.sym_off = dp.sym_off; S.sym_data = dp.sym_data;
     S.offsets = (uint64_t*)d_off.ptr();
     S.err = (rh::SplitErr*)(d_tab.ptr() + o_err);
     S.first_bad = (unsigned long long*)(d_tab.ptr() + o_bad);
     if (rh_split_lds_bytes(S.list_depth) > 160 * 1024 - 512) throw rh::SchemaError("schema needs more LDS than a CDNA4 workgroup has");
+    unsigned long long slots[rh::kFilterSlots] = {};
+    if (W) {
+      const uint64_t o_kept = align_up(8 * rh::filter_words(n), kAlign);
+      const uint64_t o_bytes = o_kept + align_up(8 * rh::kFilterSlots, kAlign);
+      const uint64_t o_prog = o_bytes + align_up(std::max<uint64_t>(W->f->bytes.size(), 1), kAlign);
+      d_keep = Lease(dev_pool(), o_prog + align_up(sizeof(rh::FilterProgram), kAlign), device);
+      SW.keep = (uint64_t*)d_keep.ptr(); SW.kept = (unsigned long long*)(d_keep.ptr() + o_kept); SW.cbytes = d_keep.ptr() + o_bytes;
+      SW.flt = (const rh::FilterProgram*)(d_keep.ptr() + o_prog);
+      HIPCHK(hipMemsetAsync(d_keep.ptr(), 0, o_bytes, stream));      // (the lanes OR their bits into zeroed words)
+      HIPCHK(hipMemcpyAsync(d_keep.ptr() + o_prog, &W->f->prog, sizeof(rh::FilterProgram), hipMemcpyHostToDevice, stream));
+      if (!W->f->bytes.empty()) HIPCHK(hipMemcpyAsync(d_keep.ptr() + o_bytes, W->f->bytes.data(), W->f->bytes.size(), hipMemcpyHostToDevice, stream));
+    }
     Events ev;
     ev.init();
     ev.rec(0, stream);
-    if (rh_launch_split(&S, stream)) throw HipError("k_split launch failed");
+    if (W) {
+      if (rh_launch_split_where(&SW, stream)) throw HipError("k_split_where launch failed");
+    } else if (rh_launch_split(&S, stream)) throw HipError("k_split launch failed");
     ev.rec(1, stream);
     unsigned long long fb = 0;
     HIPCHK(hipMemcpyAsync(&fb, S.first_bad, 8, hipMemcpyDeviceToHost, stream));
+    if (W) HIPCHK(hipMemcpyAsync(slots, SW.kept, sizeof slots, hipMemcpyDeviceToHost, stream));
     HIPCHK(hipStreamSynchronize(stream));
     split_ms = ev.ms(0, 1);
     if (fb) {
@@ -152,8 +190,41 @@ static rh_device_result* split_and_decode(rh_schema* s, rh_schema* plain, Lease&
           throw DecodeError(block_end_message(b, first[b + 1] - first[b], errs[b].detail, end[b] - start[b]));
       throw std::runtime_error("internal error: the split kernel reported a failure no block owns");
     }
+    if (W) {
+      W->kept = 0;
+      for (uint32_t i = 0; i < rh::kFilterSlots; i++) W->kept += slots[i];
+      if (W->kept > n) throw std::runtime_error("internal error: the filter kept more records than it was given");
+    }
   }
   g_split_last_ms.store(split_ms);
+
+  if (W && W->mask_only) {
+    if (n && W->keep_words) HIPCHK(hipMemcpy(W->keep_words, d_keep.ptr(), 8 * rh::filter_words(n), hipMemcpyDeviceToHost));
+    note_where(split_ms, 0, n, W->kept);
+    return nullptr;
+  }
+  if (W && W->kept != n) {
+    Compacted c;
+    compact_kept(d_data.ptr(), (const uint64_t*)d_off.ptr(), data_end, n, (const uint64_t*)d_keep.ptr(), W->kept, device, stream, c);
+    note_where(split_ms, c.ms, n, W->kept);
+    d_keep.release();
+    d_data.release();      // (the kept records have buffers of their own: the file goes back to the pool before the decode)
+    d_off.release();
+    rh_device_result* r;
+    try {
+      r = decode_device_impl(s, c.data.ptr(), (const uint64_t*)c.off.ptr(), c.len, W->kept, num_chunks, opts, stats);
+    } catch (const RecordDecodeError& e) {
+      throw std::runtime_error(std::string("internal error: a record the split accepted failed to decode: ") + e.what());
+    }
+    r->patched_data = std::move(c.data);      // the result owns the compacted buffers, as a filtered list call's
+    r->patched_offsets = std::move(c.off);
+    if (stats) stats->h2d_ms += up_ms;
+    return r;
+  }
+  if (W) {
+    note_where(split_ms, 0, n, W->kept);
+    d_keep.release();
+  }
 
   rh_device_result* r = decode_device_impl(s, d_data.ptr(), (const uint64_t*)d_off.ptr(), data_end, n, num_chunks, opts, stats);
   r->container_data = std::move(d_data);      // the result owns every byte its call read (as a repaired tolerant call's)
@@ -163,8 +234,10 @@ static rh_device_result* split_and_decode(rh_schema* s, rh_schema* plain, Lease&
 }
 
 static rh_device_result* decode_blocks_impl(rh_schema* s, const uint8_t* data, uint64_t len, const uint64_t* start, const uint64_t* end,
-                                            const uint64_t* first, uint64_t nb, uint64_t num_chunks, const rh_opts* opts, rh_stats* stats) {
+                                            const uint64_t* first, uint64_t nb, uint64_t num_chunks, const rh_opts* opts, rh_stats* stats,
+                                            WhereCall* W = nullptr) {
   check_blocks_call(opts, data, start, end, first, nb);
+  if (W) check_filter(s, W->f);
   rh_schema* const plain = plain_schema(s);
   const uint64_t min_rec = plain->cs->min_record_bytes;
   for (uint64_t b = 0; b < nb; b++) {
@@ -190,7 +263,7 @@ static rh_device_result* decode_blocks_impl(rh_schema* s, const uint8_t* data, u
   T.upload(start, end, first, nb, n, device, stream);
   HIPCHK(hipStreamSynchronize(stream));      // (the sources are the caller's pageable memory)
   const float up_ms = t_up.ms();
-  return split_and_decode(s, plain, d_data, len, T, start, end, first, nb, num_chunks, opts, stats, device, stream, up_ms);
+  return split_and_decode(s, plain, d_data, len, T, start, end, first, nb, num_chunks, opts, stats, device, stream, up_ms, W);
 }
 
 // ---- deflate blocks on the device (inflate.hip) ------------------------------------------------------------------
@@ -417,10 +490,11 @@ static void deflate_on_device(const uint8_t* data, uint64_t len, const uint64_t*
 
 static rh_device_result* decode_cblocks_impl(rh_schema* s, const uint8_t* data, uint64_t len, const uint64_t* start, const uint64_t* end,
                                              const uint64_t* first, uint64_t nb, int codec, uint64_t max_block_bytes, uint64_t num_chunks,
-                                             const rh_opts* opts, rh_stats* stats) {
-  if (codec == RH_CODEC_NULL) return decode_blocks_impl(s, data, len, start, end, first, nb, num_chunks, opts, stats);
+                                             const rh_opts* opts, rh_stats* stats, WhereCall* W = nullptr) {
+  if (codec == RH_CODEC_NULL) return decode_blocks_impl(s, data, len, start, end, first, nb, num_chunks, opts, stats, W);
   if (codec != RH_CODEC_DEFLATE) throw std::invalid_argument("container: codec must be RH_CODEC_NULL or RH_CODEC_DEFLATE");
   check_blocks_call(opts, data, start, end, first, nb);
+  if (W) check_filter(s, W->f);
   rh_schema* const plain = plain_schema(s);
   const uint64_t min_rec = plain->cs->min_record_bytes;
   check_compressed_table(start, end, nb, len);
@@ -454,7 +528,7 @@ static rh_device_result* decode_cblocks_impl(rh_schema* s, const uint8_t* data, 
   T.upload(istart.data(), iend.data(), first, nb, n, device, stream);
   HIPCHK(hipStreamSynchronize(stream));      // (istart / iend are this frame's)
   const float up_ms = t_up.ms() - I.size_ms - I.emit_ms;
-  return split_and_decode(s, plain, I.d_out, I.total, T, istart.data(), iend.data(), first, nb, num_chunks, opts, stats, device, stream, up_ms);
+  return split_and_decode(s, plain, I.d_out, I.total, T, istart.data(), iend.data(), first, nb, num_chunks, opts, stats, device, stream, up_ms, W);
 }
 
 // ---- tolerant reads -------------------------------------------------------------------------------------------
@@ -890,6 +964,92 @@ int rh_decode_cblocks(const rh_schema* s, const uint8_t* data, uint64_t len, con
     if (stats) stats->total_ms = t.ms();
     return rc;
   });
+}
+
+// ---- row filters in the split walk ------------------------------------------------------------------------------
+int rh_decode_cblocks_device_where(const rh_schema* s, const uint8_t* data, uint64_t len, const uint64_t* start, const uint64_t* end,
+                                   const uint64_t* first, uint64_t nb, int codec, uint64_t max_block_bytes, uint64_t num_chunks,
+                                   const rh_opts* opts, rh_device_result** out, rh_stats* stats, char** err, const rh_filter* filter,
+                                   uint64_t* kept) {
+  if (!s || !out || !filter) return RH_ERR_ARGUMENT;
+  *out = nullptr;
+  return guarded(err, [&] {
+    Timer t;
+    rh_opts pub;
+    if (opts) { pub = *opts; pub.flags &= kPublicFlags; }
+    WhereCall W;
+    W.f = const_cast<rh_filter*>(filter);
+    *out = decode_cblocks_impl(const_cast<rh_schema*>(s), data, len, start, end, first, nb, codec, max_block_bytes, num_chunks,
+                               opts ? &pub : nullptr, stats, &W);
+    if (kept) *kept = W.kept;
+    if (stats) stats->total_ms = t.ms();
+    return RH_OK;
+  });
+}
+
+int rh_decode_cblocks_where(const rh_schema* s, const uint8_t* data, uint64_t len, const uint64_t* start, const uint64_t* end,
+                            const uint64_t* first, uint64_t nb, int codec, uint64_t max_block_bytes, uint64_t num_chunks, const rh_opts* opts,
+                            struct ArrowArray* out_chunks, uint32_t* out_k, rh_stats* stats, char** err, const rh_filter* filter,
+                            uint64_t* kept) {
+  if (!s || !out_chunks || !filter) return RH_ERR_ARGUMENT;
+  return guarded(err, [&] {
+    Timer t;
+    rh_opts pub;
+    if (opts) { pub = *opts; pub.flags &= kPublicFlags; }
+    WhereCall W;
+    W.f = const_cast<rh_filter*>(filter);
+    std::unique_ptr<rh_device_result> r(decode_cblocks_impl(const_cast<rh_schema*>(s), data, len, start, end, first, nb, codec, max_block_bytes,
+                                                            num_chunks, opts ? &pub : nullptr, stats, &W));
+    if (kept) *kept = W.kept;
+    Timer td;
+    const int rc = to_host_impl(r.get(), out_chunks, opts ? (hipStream_t)opts->stream : nullptr);
+    if (stats) stats->d2h_ms = td.ms();
+    if (out_k) *out_k = r->k;
+    if (stats) stats->total_ms = t.ms();
+    return rc;
+  });
+}
+
+int rh_decode_blocks_device_where(const rh_schema* s, const uint8_t* data, uint64_t len, const uint64_t* start, const uint64_t* end,
+                                  const uint64_t* first, uint64_t nb, uint64_t num_chunks, const rh_opts* opts, rh_device_result** out,
+                                  rh_stats* stats, char** err, const rh_filter* filter, uint64_t* kept) {
+  return rh_decode_cblocks_device_where(s, data, len, start, end, first, nb, RH_CODEC_NULL, 0, num_chunks, opts, out, stats, err, filter, kept);
+}
+
+int rh_decode_blocks_where(const rh_schema* s, const uint8_t* data, uint64_t len, const uint64_t* start, const uint64_t* end,
+                           const uint64_t* first, uint64_t nb, uint64_t num_chunks, const rh_opts* opts, struct ArrowArray* out_chunks,
+                           uint32_t* out_k, rh_stats* stats, char** err, const rh_filter* filter, uint64_t* kept) {
+  return rh_decode_cblocks_where(s, data, len, start, end, first, nb, RH_CODEC_NULL, 0, num_chunks, opts, out_chunks, out_k, stats, err, filter,
+                                 kept);
+}
+
+int rh_filter_cblocks(const rh_filter* f, const uint8_t* data, uint64_t len, const uint64_t* start, const uint64_t* end, const uint64_t* first,
+                      uint64_t nb, int codec, uint64_t max_block_bytes, const rh_opts* opts, uint64_t* keep_words, uint64_t* kept, char** err) {
+  if (!f) return RH_ERR_ARGUMENT;
+  return guarded(err, [&] {
+    rh_opts pub;
+    if (opts) { pub = *opts; pub.flags &= kPublicFlags; }
+    WhereCall W;
+    W.f = const_cast<rh_filter*>(f);
+    W.mask_only = true;
+    W.keep_words = keep_words;
+    decode_cblocks_impl(f->plain, data, len, start, end, first, nb, codec, max_block_bytes, 1, opts ? &pub : nullptr, nullptr, &W);
+    if (kept) *kept = W.kept;
+    return RH_OK;
+  });
+}
+
+int rh_filter_blocks(const rh_filter* f, const uint8_t* data, uint64_t len, const uint64_t* start, const uint64_t* end, const uint64_t* first,
+                     uint64_t nb, const rh_opts* opts, uint64_t* keep_words, uint64_t* kept, char** err) {
+  return rh_filter_cblocks(f, data, len, start, end, first, nb, RH_CODEC_NULL, 0, opts, keep_words, kept, err);
+}
+
+void rh_container_where_last(float* split_ms, float* gather_ms, uint64_t* n, uint64_t* kept) {
+  std::lock_guard<std::mutex> g(g_where_last_mu);
+  if (split_ms) *split_ms = g_where_last.split_ms;
+  if (gather_ms) *gather_ms = g_where_last.gather_ms;
+  if (n) *n = g_where_last.n;
+  if (kept) *kept = g_where_last.kept;
 }
 
 int rh_inflate_blocks(const uint8_t* data, uint64_t len, const uint64_t* start, const uint64_t* end, uint64_t nb, uint64_t max_block_bytes,

@@ -14,13 +14,6 @@ int rh_launch_filter_gather(const rh::CParams* G, void* stream);
 
 using namespace rhe;
 
-struct rh_filter {
-  rh::FilterProgram prog;
-  std::vector<uint8_t> bytes;      // the byte comparands (FilterTerm::boff / blen)
-  std::string json;                // the writer schema's text: what a call's schema must have been made from
-  rh_schema* plain = nullptr;      // a plain compile of it, the filter's own: the program rh_k_filter walks
-};
-
 namespace rhe {
 
 // ---------------------------------------------------------------------------
@@ -248,8 +241,40 @@ static void filter_device_range(rh_filter* f, int device, hipStream_t stream, co
   out.ws = std::move(ws);
 }
 
-static void check_filter(const rh_schema* s, const rh_filter* f) {
+void check_filter(const rh_schema* s, const rh_filter* f) {
   if (s->cs->json != f->json) throw std::invalid_argument("where: the predicate was compiled against another writer schema");
+}
+
+void compact_kept(const uint8_t* d_data, const uint64_t* d_offsets, uint64_t data_len, uint64_t n, const uint64_t* d_keep, uint64_t kept,
+                  int device, hipStream_t stream, Compacted& out) {
+  rh::CParams G;
+  std::memset(&G, 0, sizeof G);
+  G.data = d_data; G.offsets = d_offsets; G.n = n; G.keep = d_keep;
+  G.nblocks = (uint32_t)((n + rh::kFilterBlock - 1) / rh::kFilterBlock);
+  const uint64_t o_bytes = align_up(8ull * G.nblocks, kAlign);
+  const uint64_t o_rank = align_up(o_bytes + 8ull * G.nblocks, kAlign);
+  Lease small(dev_pool(), o_rank + 8 * rh::filter_words(n), device);
+  Lease new_off(dev_pool(), 8 * (kept + 1), device);
+  G.blockcnt = (uint64_t*)small.ptr(); G.blockbytes = (uint64_t*)(small.ptr() + o_bytes); G.wordrank = (uint64_t*)(small.ptr() + o_rank);
+  G.new_offsets = (uint64_t*)new_off.ptr();
+  Events ev;
+  ev.init();
+  ev.rec(0, stream);
+  if (rh_launch_filter_offsets(&G, stream)) throw HipError("filter (offsets) launch failed");
+  uint64_t new_len = 0;
+  HIPCHK(hipMemcpyAsync(&new_len, G.new_offsets + kept, 8, hipMemcpyDeviceToHost, stream));
+  HIPCHK(hipStreamSynchronize(stream));
+  if (new_len > data_len) throw std::runtime_error("internal error: the kept records are larger than the input");
+  Lease new_data(dev_pool(), new_len + 64, device);
+  G.out = new_data.ptr();
+  if (rh_launch_filter_gather(&G, stream)) throw HipError("filter (gather) launch failed");
+  ev.rec(1, stream);
+  HIPCHK(hipMemsetAsync(new_data.ptr() + new_len, 0, 64, stream));
+  HIPCHK(hipStreamSynchronize(stream));      // (a call that deals its chunk groups to internal streams reads the input from those)
+  out.ms = ev.ms(0, 1);
+  out.len = new_len;
+  out.data = std::move(new_data);
+  out.off = std::move(new_off);
 }
 
 // filter -> (errors) -> kept == n: the input as it is | compact -> the strict decode of the compacted list
@@ -267,41 +292,18 @@ static rh_device_result* decode_device_where(rh_schema* s, rh_filter* f, const u
     fl.ws.release();
     return decode_device_impl(s, d_data, d_offsets, data_len, n, num_chunks, opts, stats);
   }
-  rh::CParams G;
-  std::memset(&G, 0, sizeof G);
-  G.data = d_data; G.offsets = d_offsets; G.n = n; G.keep = (const uint64_t*)fl.ws.ptr();
-  G.nblocks = (uint32_t)((n + rh::kFilterBlock - 1) / rh::kFilterBlock);
-  const uint64_t o_bytes = align_up(8ull * G.nblocks, kAlign);
-  const uint64_t o_rank = align_up(o_bytes + 8ull * G.nblocks, kAlign);
-  Lease small(dev_pool(), o_rank + 8 * rh::filter_words(n), device);
-  Lease new_off(dev_pool(), 8 * (fl.kept + 1), device);
-  G.blockcnt = (uint64_t*)small.ptr(); G.blockbytes = (uint64_t*)(small.ptr() + o_bytes); G.wordrank = (uint64_t*)(small.ptr() + o_rank);
-  G.new_offsets = (uint64_t*)new_off.ptr();
-  Events ev;
-  ev.init();
-  ev.rec(0, stream);
-  if (rh_launch_filter_offsets(&G, stream)) throw HipError("filter (offsets) launch failed");
-  uint64_t new_len = 0;
-  HIPCHK(hipMemcpyAsync(&new_len, G.new_offsets + fl.kept, 8, hipMemcpyDeviceToHost, stream));
-  HIPCHK(hipStreamSynchronize(stream));
-  if (new_len > data_len) throw std::runtime_error("internal error: the kept records are larger than the input");
-  Lease new_data(dev_pool(), new_len + 64, device);
-  G.out = new_data.ptr();
-  if (rh_launch_filter_gather(&G, stream)) throw HipError("filter (gather) launch failed");
-  ev.rec(1, stream);
-  HIPCHK(hipMemsetAsync(new_data.ptr() + new_len, 0, 64, stream));
-  HIPCHK(hipStreamSynchronize(stream));      // (a call that deals its chunk groups to internal streams reads the input from those)
-  note_last(fl.filter_ms, ev.ms(0, 1), n, fl.kept);
+  Compacted c;
+  compact_kept(d_data, d_offsets, data_len, n, (const uint64_t*)fl.ws.ptr(), fl.kept, device, stream, c);
+  note_last(fl.filter_ms, c.ms, n, fl.kept);
   fl.ws.release();
-  small.release();
   rh_device_result* r;
   try {
-    r = decode_device_impl(s, new_data.ptr(), (const uint64_t*)new_off.ptr(), new_len, fl.kept, num_chunks, opts, stats);
+    r = decode_device_impl(s, c.data.ptr(), (const uint64_t*)c.off.ptr(), c.len, fl.kept, num_chunks, opts, stats);
   } catch (const RecordDecodeError& e) {
     throw std::runtime_error(std::string("internal error: a record the filter accepted failed to decode: ") + e.what());
   }
-  r->patched_data = std::move(new_data);      // the result owns every byte its call read (as a repaired tolerant call's)
-  r->patched_offsets = std::move(new_off);
+  r->patched_data = std::move(c.data);      // the result owns every byte its call read (as a repaired tolerant call's)
+  r->patched_offsets = std::move(c.off);
   return r;
 }
 

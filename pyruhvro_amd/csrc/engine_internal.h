@@ -43,6 +43,7 @@ extern "C" hipError_t hipExtModuleLaunchKernel(hipFunction_t f, uint32_t globalW
 #include "kernel_jobs.h"
 #include "rtc_compile.h"
 #include "encode.h"
+#include "filter_core.h"    // FilterProgram: what a compiled predicate (rh_filter) holds
 
 extern "C" {
 // start / stop: optional hipEvent_t that receive the kernel's own begin / end timestamps (hipExtLaunchKernelGGL): no
@@ -755,5 +756,32 @@ struct Uploaded {
   uint64_t bytes = 0;
 };
 void upload(const Source& src, uint64_t n, int device, hipStream_t stream, Uploaded& u);
+
+}  // namespace rhe
+
+// A compiled predicate (engine_filter.cpp rh_filter_compile).  Read by the filtered list calls there and by the
+// filtered container reads (engine_container.cpp).
+struct rh_filter {
+  rh::FilterProgram prog;
+  std::vector<uint8_t> bytes;      // the byte comparands (FilterTerm::boff / blen)
+  std::string json;                // the writer schema's text: what a call's schema must have been made from
+  rh_schema* plain = nullptr;      // a plain compile of it, the filter's own: the program the predicate's pcs point into
+};
+
+namespace rhe {
+
+// refuses a schema that was not made from the writer text the predicate was compiled against
+void check_filter(const rh_schema* s, const rh_filter* f);
+
+// The compaction of a filtered call (engine_filter.cpp): the records of (d_data, d_offsets, n) whose bit is set in d_keep
+// (FParams::keep's format, `kept` of them) gathered into buffers of their own -- rh_launch_filter_offsets, one synchronisation
+// for the kept bytes, rh_launch_filter_gather.  Complete (synchronised) on return; ms = GPU time of the launches.
+struct Compacted {
+  Lease data, off;       // the kept records back to back (+ 64 zero bytes), kept + 1 offsets that start at 0
+  uint64_t len = 0;
+  float ms = 0;
+};
+void compact_kept(const uint8_t* d_data, const uint64_t* d_offsets, uint64_t data_len, uint64_t n, const uint64_t* d_keep, uint64_t kept,
+                  int device, hipStream_t stream, Compacted& out);
 
 }  // namespace rhe

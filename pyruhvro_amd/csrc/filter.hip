@@ -12,7 +12,8 @@
 //                        in front of every keep word.
 //   rh_k_filter_gather   the kept records copied to their new places: one wavefront per 64 records, every run of kept neighbours
 //                        as ONE copy, 16-byte vectors aligned on the destination, bytes at the ragged ends.
-// Small helpers of validate.hip (the program fetch, the block scan, the wavefront copy) are restated here: that file stays as it is.
+// Small helpers of validate.hip (the block scan, the wavefront copy) are restated here: that file stays as it is.  The walk and the
+// evaluation of a term (filter_walk, f_eval, f_varint, the program fetch) are in filter_eval.h, shared with rh_k_split_where.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -23,6 +24,7 @@
 #include "walk.h"
 #include "walk_drop.h"
 #include "filter.h"
+#include "filter_eval.h"      // f_varint / f_eval / filter_walk: shared with rh_k_split_where (container.hip)
 
 namespace rh {
 
@@ -40,123 +42,6 @@ struct FCtx {
   bool wave_live;
   __device__ __forceinline__ uint32_t& remaining(int d) const { return rem[d * kBlock + tid]; }
 };
-
-typedef const __attribute__((address_space(4))) Op* FProgPtr;
-__device__ __forceinline__ Op f_ld_op(FProgPtr p) {
-  Op o;
-  o.code = p->code; o.flags = p->flags; o.dom = p->dom; o.a = p->a; o.b = p->b; o.c = p->c;
-  o.buf0 = p->buf0; o.buf1 = p->buf1; o.buf2 = p->buf2; o.node = p->node;
-  return o;
-}
-
-// A varint the careful walk has accepted, read again at p: its value and its bytes.  Up to 8 bytes in one read; a longer or
-// padded one byte by byte, ten turns whatever the bytes are (the tenth byte gives bit 63 only, as the walk reads it).
-template <class Src>
-__device__ __forceinline__ uint32_t f_varint(const Src& src, uint32_t p, bool act, int64_t& v) {
-  uint32_t n = 1;
-  v = 0;
-  const bool ok = varint64(src.ld8(p), 8, 0x7FFFFFFFu, v, n);
-  if (__any(act && !ok)) {
-    if (act && !ok) {
-      uint64_t r = 0;
-      bool done = false;
-      n = 0;
-      for (uint32_t k = 0; k < 10; k++) {
-        if (!done) {
-          const uint32_t b = src.ld1(p + k);
-          r |= (uint64_t)(b & 0x7Fu) << (7u * k);
-          n = k + 1;
-          done = (b & 0x80u) == 0;
-        }
-      }
-      v = (int64_t)(r >> 1) ^ -(int64_t)(r & 1);
-    }
-  }
-  return n;
-}
-
-// The terms `tm` (a wave-uniform bit set) of the field whose bytes start at p, for the lanes with `act` (a record, no error).
-template <class Src>
-__device__ __forceinline__ bool f_eval(const FParams& F, const Src& src, const Op& op, uint32_t tm, uint32_t p, bool act) {
-  uint32_t kind = 0;
-#pragma unroll
-  for (uint32_t t = 0; t < kMaxFilterTerms; t++)
-    if ((tm >> t) & 1u) kind = F.flt.term[t].kind;      // (every term of one field has the field's kind)
-  bool isnull = false;
-  if (op.flags & F_NULLABLE) {
-    int64_t idx = 0;
-    p += f_varint(src, p, act, idx);
-    isnull = filter_branch_null(idx, (op.flags & F_NULL_FIRST) != 0);
-  }
-  const bool val = act && !isnull;
-  int64_t iv = 0;
-  double dv = 0.0;
-  uint64_t vlen = 0;
-  uint32_t vpos = p;
-  switch (kind) {      // (wave-uniform)
-    case FLT_I32: case FLT_I64: case FLT_ENUM: {
-      int64_t x = 0;
-      f_varint(src, p, val, x);
-      iv = kind == FLT_I32 ? filter_int32(x) : x;
-      break;
-    }
-    case FLT_F32: dv = (double)__uint_as_float(src.ld4(p)); break;
-    case FLT_F64: dv = __longlong_as_double((long long)src.ld8(p)); break;
-    case FLT_BOOL: iv = (src.ld1(p) & 0xFFu) != 0 ? 1 : 0; break;
-    default: {           // FLT_BYTES
-      int64_t len = 0;
-      const uint32_t nb = f_varint(src, p, val, len);
-      vlen = val ? (uint64_t)len : 0ull;
-      vpos = p + nb;
-      break;
-    }
-  }
-  bool keep = true;
-#pragma unroll
-  for (uint32_t t = 0; t < kMaxFilterTerms; t++) {
-    if (!((tm >> t) & 1u)) continue;
-    const uint32_t cmp = F.flt.term[t].cmp;
-    bool k;
-    switch (kind) {
-      case FLT_I32: case FLT_I64: k = term_keeps_int(cmp, isnull, iv, F.flt.term[t].i); break;
-      case FLT_ENUM: case FLT_BOOL: k = term_keeps_index(cmp, isnull, iv, F.flt.term[t].i); break;
-      case FLT_F32: case FLT_F64: k = term_keeps_f64(cmp, isnull, dv, F.flt.term[t].d); break;
-      default: {
-        const auto get = [src, vpos](uint32_t i) { return src.ld1(vpos + i); };      // (asked for i < vlen only: inside the value)
-        k = term_keeps_bytes(cmp, isnull, get, vlen, F.cbytes + F.flt.term[t].boff, F.flt.term[t].blen);
-        break;
-      }
-    }
-    keep = keep && k;
-  }
-  return keep;
-}
-
-// the program, every op counters-only and careful (walk_drop.h run_dropped); returns whether the lane's record matches
-template <class Src>
-__device__ __forceinline__ bool filter_walk(const FParams& F, const FCtx& c, const Src& src, Lane& L, bool mine) {
-  const FProgPtr prog = reinterpret_cast<FProgPtr>(reinterpret_cast<uintptr_t>(F.prog));
-  bool keep = mine;
-  int pc = 0;
-  for (;;) {
-    pc = __builtin_amdgcn_readfirstlane(pc);
-    const Op op = f_ld_op(prog + pc);
-    if (op.code == OP_END) return keep;
-    int npc = op.code == OP_LIST_TAIL ? op.b : pc + 1;      // LIST_TAIL goes back to its LIST_NEXT
-    if (op.code > OP_BIN) return keep;
-    uint32_t tm = 0;                                        // the terms that mark this op (wave-uniform)
-#pragma unroll
-    for (uint32_t t = 0; t < kMaxFilterTerms; t++)
-      if (t < F.flt.nterms && F.flt.term[t].pc == pc) tm |= 1u << t;
-    const uint32_t cur0 = L.cur;
-    if (!run_dropped<false, true>(c, src, L, op)) npc = op.b;      // no lane has an item left: to LIST_END
-    if (tm) {
-      const bool k = f_eval(F, src, op, tm, cur0, mine && L.err == 0);
-      keep = keep && k;
-    }
-    pc = npc;
-  }
-}
 
 extern "C" __global__ void __launch_bounds__(kBlock) rh_k_filter(FParams F) {
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
@@ -186,15 +71,16 @@ extern "C" __global__ void __launch_bounds__(kBlock) rh_k_filter(FParams F) {
   c.rem = rem; c.sym_off = F.sym_off; c.sym_data = F.sym_data;
   c.lrow = (uint32_t)g.lrow0 + tid; c.tid = tid; c.lane = lane; c.wave_live = (wave * 64) < g.nrec;
   const bool mine = tid < g.nrec;
+  const FMarks marks = f_marks(F.flt);
   bool keep;
   if (fits) {
     const uint32_t wa = (uint32_t)(uintptr_t)(RH_LDS uint8_t*)win;
     L.cur += wa; L.end += wa;
     LdsAbsSrc src;
-    keep = filter_walk(F, c, src, L, mine);
+    keep = filter_walk(F.prog, &F.flt, marks, F.cbytes, c, src, L, mine);
   } else {
     GlobalSrc src{F.data + wb16, F.data_len - wb16};
-    keep = filter_walk(F, c, src, L, mine);
+    keep = filter_walk(F.prog, &F.flt, marks, F.cbytes, c, src, L, mine);
   }
 
   const uint64_t rec = g.rec0 + tid;
