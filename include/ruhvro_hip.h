@@ -313,6 +313,11 @@ int rh_encode(const rh_schema* s, const struct ArrowArray* batch, const struct A
 typedef struct rh_device_encoded rh_device_encoded;
 int rh_encode_device(const rh_schema* s, const struct ArrowArray* batch, const struct ArrowSchema* batch_schema,
                      uint64_t num_chunks, const rh_opts* opts, rh_device_encoded** out, rh_stats* stats, char** err);
+/* rh_encode with the result left in HBM (symbol added without a change of RH_ABI_VERSION): `batch` is a HOST batch, as
+ * rh_encode's, and the BinaryArrays are an rh_device_encoded, as rh_encode_device's.  What rh_frame_join reads: the encoded
+ * datums of a framed write cross PCIe once, as finished messages. */
+int rh_encode_to_device(const rh_schema* s, const struct ArrowArray* batch, const struct ArrowSchema* batch_schema,
+                        uint64_t num_chunks, const rh_opts* opts, rh_device_encoded** out, rh_stats* stats, char** err);
 uint32_t rh_device_encoded_chunks(const rh_device_encoded* r);
 uint64_t rh_device_encoded_output_bytes(const rh_device_encoded* r);   /* exact: i32 offsets + Avro bytes, all chunks */
 int rh_device_encoded_export(rh_device_encoded* r, uint32_t chunk, struct ArrowDeviceArray* out);
@@ -699,6 +704,31 @@ int rh_frame_decode_class(rh_frame_split* split, uint32_t c, const rh_schema* s,
                           struct ArrowArray* out_chunks, uint32_t* out_k, rh_stats* stats, char** err);
 void rh_frame_split_free(rh_frame_split* split);
 void rh_frame_last(float* classify_ms, float* scan_offsets_ms, float* gather_ms, uint64_t* n);
+
+/* Framed messages, the write side (symbols added without a change of RH_ABI_VERSION: look them up by name).
+ * rh_frame_join: the datums of `nsrc` sources -- each one chunk of a device-resident encode result -- become n messages, every
+ * datum behind the header of `framing` that carries its source's wire id, produced in HBM.  Without indices the messages are the
+ * sources' rows in the order given; with indices (host memory, one int64 per row of that chunk, on every source that has rows or
+ * on none) row j of a source becomes message indices[j], and the indices together must be a permutation of 0 .. n-1.  n must be
+ * the rows of all sources together; the sources live on one device.  The result is an rh_device_encoded of
+ * rh_clamp_chunks(n, num_chunks) BinaryArrays, chunked as rh_encode chunks n rows: rh_device_encoded_export / _to_host /
+ * _output_bytes / _free apply.  The sources are read, not consumed.  The source table lies in device memory: nsrc is not bounded by
+ * kernel-argument space.
+ * Failures (RH_ERR_DECODE, the message starts with "framed: "): the first index outside 0 .. n-1 (the lowest source row in the
+ * order given) "schema id {id}: index {v} is outside 0 .. {n-1}"; else the lowest position that is not named exactly once,
+ * "position {p} is named more than once" / "position {p} is never named"; a chunk whose messages pass 2^31-1 bytes names the
+ * chunk.  rh_opts.devices and RH_ASYNC are refused with RH_ERR_ARGUMENT.
+ * rh_frame_join_last: GPU time of the most recent join's lengths kernel, of its three prefix kernels, and of its gather. */
+typedef struct rh_frame_source {
+  const rh_device_encoded* enc;
+  uint32_t chunk;
+  uint32_t pad;
+  uint64_t id;              /* the wire id, unsigned (a confluent id lies in 0 .. 2^32-1) */
+  const int64_t* indices;   /* host, one per row of that chunk, or NULL */
+} rh_frame_source;
+int rh_frame_join(const rh_frame_source* src, uint32_t nsrc, uint32_t framing, uint64_t n, uint64_t num_chunks, const rh_opts* opts,
+                  rh_device_encoded** out, char** err);
+void rh_frame_join_last(float* lengths_ms, float* scan_ms, float* gather_ms, uint64_t* n);
 
 /* Measurement hook, not part of the drop-in surface: the host-side gather of a `shards`-GPU rh_decode call (every shard's
  * record slices copied into its staging buffer by its own host thread + `threads_per_shard` helpers, all shards at once)

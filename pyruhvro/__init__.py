@@ -10,9 +10,11 @@ object container files: ``container_info`` / ``read_container`` / ``read_contain
 ``filter_container``, which evaluate a ``where`` predicate in the walk that finds the file's records; and framed
 messages as a Kafka consumer holds them (Confluent wire format, Avro single-object encoding): ``deserialize_framed`` splits them
 by writer schema id on the GPU and decodes every group, ``frame_split`` is that split alone, ``schema_fingerprint`` the id a
-single-object header carries."""
+single-object header carries, and ``serialize_framed`` the way back: record batches of several writer schemas encoded, put into
+message order and given their headers on the GPU."""
 from pyruhvro_amd import (  # noqa: F401
     deserialize_framed,
+    serialize_framed,
     frame_split,
     schema_fingerprint,
     FramedGroup,
@@ -48,5 +50,5 @@ __all__ = [
     "deserialize_array_tolerant", "deserialize_array_threaded_tolerant", "deserialize_binary_array_tolerant",
     "container_info", "read_container", "read_container_to_device", "write_container", "read_container_tolerant",
     "read_container_to_device_tolerant", "BlockError", "read_container_where", "read_container_where_to_device", "filter_container",
-    "deserialize_framed", "frame_split", "schema_fingerprint", "FramedGroup", "FramedResult",
+    "deserialize_framed", "frame_split", "schema_fingerprint", "FramedGroup", "FramedResult", "serialize_framed",
 ]

@@ -447,13 +447,13 @@ __all__ = [
     "container_info", "read_container", "read_container_to_device", "write_container", "ContainerInfo",
     "read_container_tolerant", "read_container_to_device_tolerant", "BlockError",
     "read_container_where", "read_container_where_to_device", "filter_container",
-    "deserialize_framed", "frame_split", "schema_fingerprint", "FramedGroup", "FramedResult",
+    "deserialize_framed", "frame_split", "schema_fingerprint", "FramedGroup", "FramedResult", "serialize_framed",
 ]
 
 from .container import ContainerInfo, container_info, read_container, read_container_to_device, write_container  # noqa: E402
 from .container import BlockError, read_container_tolerant, read_container_to_device_tolerant  # noqa: E402
 from .container import filter_container, read_container_where, read_container_where_to_device  # noqa: E402
-from .framing import FramedGroup, FramedResult, deserialize_framed, frame_split, schema_fingerprint  # noqa: E402
+from .framing import FramedGroup, FramedResult, deserialize_framed, frame_split, schema_fingerprint, serialize_framed  # noqa: E402
 
 
 def __getattr__(name):      # (RecordError lives beside the ctypes wrappers that build it; cabi needs numpy, imported on first use)

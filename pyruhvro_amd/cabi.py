@@ -968,6 +968,78 @@ def encode_device(batch_array_addr: int, batch_schema_addr: int, schema_json: st
     return DeviceEncoded(out.value, st.as_dict())
 
 
+# Framed messages, the write side (include/ruhvro_hip.h): symbols added without a change of the ABI version.
+FRAME_JOIN_SYMBOLS = ("rh_encode_to_device", "rh_frame_join", "rh_frame_join_last")
+
+
+class RhFrameSource(C.Structure):
+    """rh_frame_source: one chunk of a device-resident encode result, the wire id its messages carry, its rows' destinations."""
+    _fields_ = [("enc", C.c_void_p), ("chunk", C.c_uint32), ("pad", C.c_uint32), ("id", C.c_uint64), ("indices", C.c_void_p)]
+
+
+def _frame_join_sym(name: str):
+    f = getattr(lib(), name, None)
+    if f is None:
+        raise RuntimeError(f"libruhvro_hip.so has no {name}: the library was built before framed writes")
+    if f.argtypes is None:
+        f.restype, f.argtypes = {
+            "rh_encode_to_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(RhOpts), C.POINTER(C.c_void_p),
+                                              C.POINTER(RhStats), C.POINTER(C.c_char_p)]),
+            "rh_frame_join": (C.c_int, [C.POINTER(RhFrameSource), C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, C.POINTER(RhOpts),
+                                        C.POINTER(C.c_void_p), C.POINTER(C.c_char_p)]),
+            "rh_frame_join_last": (None, [C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_uint64)]),
+        }[name]
+    return f
+
+
+def encode_to_device(batch, schema_json: str, num_chunks: int, device: int = -1, kernel: int = KERNEL_AUTO, devices=None,
+                     want_stats: bool = False) -> DeviceEncoded:
+    """rh_encode_to_device: a host RecordBatch (or StructArray) encoded with the result left in HBM."""
+    s = Schema.get(schema_json)
+    sa = batch.to_struct_array() if isinstance(batch, pa.RecordBatch) else batch
+    c_arr, c_sch = ArrowArray(), ArrowSchema()
+    sa._export_to_c(C.addressof(c_arr), C.addressof(c_sch))
+    out, st, err = C.c_void_p(), RhStats(), C.c_char_p()
+    opts, _keep = make_opts(device, kernel, None, devices)
+    try:
+        rc = _frame_join_sym("rh_encode_to_device")(s.handle, C.addressof(c_arr), C.addressof(c_sch), num_chunks, C.byref(opts),
+                                                    C.byref(out), C.byref(st) if want_stats else None, C.byref(err))
+    finally:
+        if c_arr.release:         # (the engine copies what it reads: the exported structs are the caller's to release)
+            C.CFUNCTYPE(None, C.POINTER(ArrowArray))(c_arr.release)(C.byref(c_arr))
+        if c_sch.release:
+            C.CFUNCTYPE(None, C.POINTER(ArrowSchema))(c_sch.release)(C.byref(c_sch))
+    if rc != RH_OK:
+        _raise(rc, err)
+    return DeviceEncoded(out.value, st.as_dict() if want_stats else {})
+
+
+def frame_join(sources, framing: int, n: int, num_chunks: int, device: int = -1, devices=None, flags: int = 0) -> DeviceEncoded:
+    """rh_frame_join.  `sources`: (DeviceEncoded, chunk, wire id, indices) in order; indices: None or a contiguous numpy int64 array
+    with one entry per row of that chunk.  -> a DeviceEncoded of rh_clamp_chunks(n, num_chunks) BinaryArrays of framed messages."""
+    arr = (RhFrameSource * max(len(sources), 1))()
+    keep = []
+    for i, (enc, chunk, wire, indices) in enumerate(sources):
+        arr[i].enc, arr[i].chunk, arr[i].pad, arr[i].id = enc.handle, chunk, 0, wire
+        if indices is not None:
+            idx = np.ascontiguousarray(indices, dtype=np.int64)
+            keep.append(idx)
+            arr[i].indices = idx.ctypes.data if len(idx) else None
+    out, err = C.c_void_p(), C.c_char_p()
+    opts, _keep = make_opts(device, flags, None, devices)
+    rc = _frame_join_sym("rh_frame_join")(arr, len(sources), framing, n, num_chunks, C.byref(opts), C.byref(out), C.byref(err))
+    if rc != RH_OK:
+        _raise(rc, err)
+    return DeviceEncoded(out.value, {})
+
+
+def frame_join_last() -> dict:
+    """rh_frame_join_last: GPU time of the most recent join of this process, stage by stage."""
+    l_ms, s_ms, g_ms, n = C.c_float(), C.c_float(), C.c_float(), C.c_uint64()
+    _frame_join_sym("rh_frame_join_last")(C.byref(l_ms), C.byref(s_ms), C.byref(g_ms), C.byref(n))
+    return {"lengths_ms": l_ms.value, "scan_ms": s_ms.value, "gather_ms": g_ms.value, "n": int(n.value)}
+
+
 def decode_device(d_data: int, d_offsets: int, data_len: int, n: int, schema_json: str, num_chunks: int,
                   device: int = -1, stream: int = 0, want_stats: bool = True, kernel: int = KERNEL_AUTO,
                   chunk_rows: int = 0, asynchronous: bool = False, two_pass: bool = False, single_pass: bool = False,

@@ -250,11 +250,12 @@ void binary_chunks_to_host(const uint8_t* d_out, uint64_t out_bytes, int device,
   }
 }
 
-// `dev_out` != nullptr: rh_encode_device -- the batch's buffers are device pointers, read in place, and the BinaryArrays
-// stay in HBM (*dev_out owns them); else rh_encode -- host batch in, host BinaryArrays out.
+// Two switches.  `dev_in`: the batch's buffers are device pointers, read in place (rh_encode_device); else they are host memory and
+// are uploaded (rh_encode, rh_encode_to_device).  `dev_out` != nullptr: the BinaryArrays stay in HBM and *dev_out owns them
+// (rh_encode_device, rh_encode_to_device); else they are copied to the host (rh_encode).
 int encode_impl(rh_schema* s, const ArrowArray* batch, const ArrowSchema* bschema, uint64_t num_chunks, const rh_opts* opts,
-                ArrowArray* out_chunks, uint32_t* out_k, rh_stats* stats, rh_device_encoded** dev_out = nullptr) {
-  const bool dev = dev_out != nullptr;
+                ArrowArray* out_chunks, uint32_t* out_k, rh_stats* stats, rh_device_encoded** dev_out = nullptr, bool dev_in = false) {
+  const bool dev = dev_in;
   const CompiledSchema& cs = *s->cs;
   if (cs.resolved) throw std::invalid_argument("a resolved schema (rh_schema_resolve) is decode only: encode with the schema the records are to be written in");
   if (cs.projected) throw std::invalid_argument("a projected schema (rh_schema_project) is decode only: encode with the full schema");
@@ -473,7 +474,7 @@ int encode_impl(rh_schema* s, const ArrowArray* batch, const ArrowSchema* bschem
 
   // ---- results: left in HBM (rh_encode_device) or -> host, one slab shared by the k BinaryArrays
   Timer td;
-  if (dev) {
+  if (dev_out) {
     auto res = std::make_unique<rh_device_encoded>();
     res->device = device; res->n = n; res->sz = sz; res->rows_last = rows_last; res->k = k;
     res->out = std::move(dout);
@@ -511,7 +512,13 @@ extern "C" int rh_encode_device(const rh_schema* s, const struct ArrowArray* bat
                                 const rh_opts* opts, rh_device_encoded** out, rh_stats* stats, char** err) {
   if (!s || !batch || !batch_schema || !out) return RH_ERR_ARGUMENT;
   *out = nullptr;
-  return guarded(err, [&] { return encode_impl(const_cast<rh_schema*>(s), batch, batch_schema, num_chunks, opts, nullptr, nullptr, stats, out); });
+  return guarded(err, [&] { return encode_impl(const_cast<rh_schema*>(s), batch, batch_schema, num_chunks, opts, nullptr, nullptr, stats, out, true); });
+}
+extern "C" int rh_encode_to_device(const rh_schema* s, const struct ArrowArray* batch, const struct ArrowSchema* batch_schema, uint64_t num_chunks,
+                                   const rh_opts* opts, rh_device_encoded** out, rh_stats* stats, char** err) {
+  if (!s || !batch || !batch_schema || !out) return RH_ERR_ARGUMENT;
+  *out = nullptr;
+  return guarded(err, [&] { return encode_impl(const_cast<rh_schema*>(s), batch, batch_schema, num_chunks, opts, nullptr, nullptr, stats, out, false); });
 }
 extern "C" uint32_t rh_device_encoded_chunks(const rh_device_encoded* r) { return r ? r->k : 0; }
 extern "C" uint64_t rh_device_encoded_output_bytes(const rh_device_encoded* r) { return r ? r->exact : 0; }

@@ -5,7 +5,9 @@
 
 ``deserialize_framed`` checks the framing, partitions the messages by writer schema and strips the headers on the GPU, then decodes
 every group with its own writer schema through the unchanged strict decode.  ``frame_split`` is that split alone, as
-``filter_records`` is the filter alone.  ``schema_fingerprint`` is the fingerprint a single-object header carries (host Python)."""
+``filter_records`` is the filter alone.  ``schema_fingerprint`` is the fingerprint a single-object header carries (host Python).
+``serialize_framed`` is the way back: record batches of several writer schemas encoded, put into message order and
+given their headers on the GPU."""
 from __future__ import annotations
 
 import json
@@ -235,3 +237,93 @@ def deserialize_framed(messages, schemas, num_chunks, *, framing="confluent", co
     first = 1 if framing == "confluent" else 2
     unknown_ids = np.array([int.from_bytes(bytes(messages[i][first:h]), byteorder) for i in unknown_indices], dtype=np.uint64)
     return FramedResult(groups, unknown_indices, unknown_ids)
+
+
+# ---- the write side -----------------------------------------------------------------------------------------------------
+def _group_parts(g, pos):
+    """One entry of `groups` -> (key, schema text, [RecordBatch], indices int64[] or None)."""
+    import pyarrow as pa
+    if isinstance(g, FramedGroup):
+        key, schema, indices, batches = g
+    elif isinstance(g, tuple) and len(g) == 3:
+        (key, schema, batches), indices = g, None
+    elif isinstance(g, tuple) and len(g) == 4:
+        key, schema, batches, indices = g
+    else:
+        raise TypeError(f"argument 'groups': group {pos} is not a FramedGroup, (id, schema, batches) or (id, schema, batches, indices)")
+    if not isinstance(schema, str):
+        raise TypeError(f"argument 'groups': group {pos}: the schema is not a str")
+    if isinstance(batches, pa.RecordBatch):
+        batches = [batches]
+    if not isinstance(batches, (list, tuple)) or not all(isinstance(b, pa.RecordBatch) for b in batches):
+        raise TypeError(f"argument 'groups': group {pos}: expected a pyarrow RecordBatch or a list of them")
+    if indices is not None:
+        try:
+            arr = np.asarray(indices)
+        except Exception:
+            raise TypeError(f"argument 'groups': group {pos}: the indices are not an int64 array") from None
+        if arr.ndim != 1 or (arr.size and arr.dtype.kind not in "iu"):
+            raise TypeError(f"argument 'groups': group {pos}: the indices are not an int64 array")
+        indices = np.ascontiguousarray(arr, dtype=np.int64)
+    return key, schema, list(batches), indices
+
+
+def serialize_framed(groups, num_chunks, *, framing="confluent"):
+    """Extension.  The mirror of ``deserialize_framed``: record batches of several writer schemas become framed messages in one
+    call.  ``groups``: a list of 1 to 32 groups, each a ``FramedGroup`` or a tuple ``(id, schema_json, batches)`` or
+    ``(id, schema_json, batches, indices)``; ``batches`` is one RecordBatch or a list of them, ``indices`` None or one int64 per
+    row of the group.  Without indices the messages are the groups' rows in the order given; with indices (on every group) row
+    ``j`` of a group becomes message ``indices[j]``, and the indices together must be a permutation of ``range(n)``.  Returns what
+    ``serialize_record_batch`` returns for a batch of ``n`` rows -- ``clamp(num_chunks, 1, max(n, 1))`` BinaryArrays -- where
+    message ``p`` is the header of ``framing`` with the group's id followed by the datum ``serialize_record_batch`` produces for
+    that row.  The rows are encoded, put into message order and given their headers on the GPU; the finished messages are what
+    comes back.  Every refusal is a ``ValueError`` that starts with ``framed: ``."""
+    import pyruhvro_amd as P
+    from . import cabi
+    if not isinstance(groups, list):
+        raise TypeError("argument 'groups': expected a list of groups")
+    _check_framing(framing)
+    if not 1 <= len(groups) <= MAX_SCHEMAS:
+        raise ValueError("framed: 1 to 32 groups per call")
+    parts = [_group_parts(g, pos) for pos, g in enumerate(groups)]
+    wire = _wire_ids([p[0] for p in parts], framing)
+    P._check_chunks(num_chunks)
+    if P._current_devices():
+        raise ValueError("framed: a framed call runs on one device (set_devices / PYRUHVRO_DEVICES is refused)")
+    for w, (_key, schema, _batches, _indices) in zip(wire, parts):
+        try:
+            P._get_schema(schema)
+        except ValueError as e:
+            raise ValueError(f"framed: schema id {w}: {e}") from None
+    given = sum(p[3] is not None for p in parts)
+    if given not in (0, len(parts)):
+        raise ValueError("framed: indices are given for some groups and not for others")
+    n = 0
+    for w, (_key, _schema, batches, indices) in zip(wire, parts):
+        rows = sum(b.num_rows for b in batches)
+        if indices is not None and len(indices) != rows:
+            raise ValueError(f"framed: schema id {w} has {rows} rows and {len(indices)} indices")
+        n += rows
+    # with indices the order of the groups does not show in the result: ascending by wire id, the order the index checks report in
+    order = sorted(range(len(parts)), key=lambda j: wire[j]) if given else range(len(parts))
+    encoded, sources = [], []
+    try:
+        for j in order:
+            _key, schema, batches, indices = parts[j]
+            at = 0
+            for b in batches:
+                try:
+                    enc = cabi.encode_to_device(b, schema, 1, kernel=P._kernel_mode)
+                except ValueError as e:
+                    raise ValueError(f"framed: schema id {wire[j]}: {e}") from None
+                encoded.append(enc)
+                sources.append((enc, 0, wire[j], None if indices is None else indices[at:at + b.num_rows]))
+                at += b.num_rows
+        joined = cabi.frame_join(sources, cabi.FRAMINGS[framing], n, num_chunks)
+        try:
+            return joined.to_host()
+        finally:
+            joined.free()
+    finally:
+        for enc in encoded:
+            enc.free()
